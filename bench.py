@@ -15,7 +15,10 @@ Gray-Scott volume at 1280x720 on one rank, VDI or --mode plain, with its own CPU
 --config 3 (vortex-in-cell |w| on a 1024^3 global grid, one z-slab per GPU), --config 4 (8 x 768^3
 bricks at 3840x2160).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4] [--dump-outputs DIR] [--full]
+  A plain run does what the headline figure needs: scene, warm-up, the K timed steps, the result line
+  (and, with --dump-outputs, the last timed step's image as DIR/image.npy).  --full adds the CPU baseline
+  (the oracle on this host's cores, ~15 s), which the result line then carries as cpu_baseline.
   N > 1 is launched by torch.distributed.run (one process per GPU, RCCL for the data path;
   a gloo group is used only to bootstrap the RCCL id and for the timing barrier).
 """
@@ -221,7 +224,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (the oracle on this "
+                         "host's cores; configs 1 and 2 on one GPU).  A plain run sets up, warms up, times the steps "
+                         "and prints the result line with cpu_baseline null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32): image.npy, the root's (H, W, 4) RGBA frame")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--brick", type=int, default=0, help="brick edge (config 2/4; default 512/768)")
     ap.add_argument("--config", type=int, default=2, choices=(1, 2, 3, 4))
@@ -444,6 +454,19 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64)
         pg.all_reduce(t, op=pg.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the root's image in the host buffer (pipelined, the
+        # flush above completed that frame into it); rgba8 as float32, 33 MB at 1920x1080.  A larger image
+        # (config 4) is cut to a fixed seeded choice of rows that fits 48 MB, listed in image_rows.npy
+        out_dir = Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        image = img_host.numpy()
+        keep = (48 << 20) // (W_IMG * 4 * 4)
+        if keep < H_IMG:
+            rows = np.sort(np.random.default_rng(1000).choice(H_IMG, keep, replace=False))
+            image = image[rows]
+            np.save(out_dir / "image_rows.npy", rows.astype(np.float64))
+        np.save(out_dir / "image.npy", image.astype(np.float32))
     mean_passes, rays_hit = ctx.pass_stats() if vdi else (1.0, 0)
     if pipelined and n_updates:   # the re-ingests' GPU time (the last batch, complete after the flush)
         gpu_send = n_updates * 1e-3 * ctx.stats()["ms_ingest"]
@@ -469,7 +492,7 @@ def main():
         achieved = alg_bytes / (ms_render * 1e-3) / 1e9
         cpu = None
         default_run = vdi and args.compositor == "flatten" and not args.merge_bricks
-        if not args.no_cpu_baseline and N == 1 and not emu and (cfg == 2 and default_run or cfg == 1):
+        if args.full and not args.no_cpu_baseline and N == 1 and not emu and (cfg == 2 and default_run or cfg == 1):
             threads = min(16, os.cpu_count() or 1)
             cpu = cpu_baseline(cams[args.warmup], vols, models, (tf, cmap), n, threads, args.cpu_budget,
                                W_IMG=W_IMG, H_IMG=H_IMG, n_total=n_units, plain=not vdi)

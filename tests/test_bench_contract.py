@@ -33,6 +33,15 @@ def test_steps_zero_rejected():
     assert p.returncode != 0 and "at least one timed step" in p.stderr, p.stderr[-2000:]
 
 
+def test_full_and_dump_outputs_are_options(tmp_path):
+    """--full and --dump-outputs DIR parse (the run then stops at the step count, before any GPU work)
+    and nothing is written before the steps have run."""
+    p = _bench(["--gpus", "1", "--full", "--dump-outputs", str(tmp_path / "out"), "--steps", "0"])
+    assert p.returncode != 0 and "at least one timed step" in p.stderr, p.stderr[-2000:]
+    assert "unrecognized arguments" not in p.stderr
+    assert not (tmp_path / "out").exists()
+
+
 def test_roofline_blocks_reproduce_from_the_committed_profile():
     """The bench line's roofline.valu and traffic come from profiles/CURRENT's summary: recomputing
     them from the summary's raw counters gives the same numbers (no GPU needed)."""

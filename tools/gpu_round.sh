@@ -2,7 +2,7 @@
 # The GPU sessions of a round, by name (run on the gpurun box: gpurun -- 'bash tools/gpu_round.sh NAME ...').
 # Every step runs under its own time limit (tools/gpu_session.sh); an A/B bench line prints the stage times.
 #   tests     all GPU tests, then smoke()
-#   bench     the default bench line (gpurun_out/bench.json)
+#   bench     the default bench line with its CPU baseline (bench.py --full; written to $BENCH_JSON, default bench.json)
 #   profile   rocprofv3 kernel trace + PMC passes of the default bench (gpurun_out/prof; tools/prof_summary.py)
 #   modes     profiles of the VDICompositor and merged-bricks modes (gpurun_out/prof_comp, prof_merged)
 #   timeline  per-ray search timeline of the one-brick share (emulated rank 7 of 8)
@@ -36,7 +36,7 @@ for name in "$@"; do
     tests) tools/gpu_session.sh \
         "gputests|700|python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread" \
         "smoke|200|python -c 'import __graft_entry__ as g; g.smoke()'" || exit $? ;;
-    bench) tools/gpu_session.sh "bench|300|python bench.py > gpurun_out/bench.json" || exit $? ;;
+    bench) tools/gpu_session.sh "bench|300|python bench.py --full > ${BENCH_JSON:-bench.json}" || exit $? ;;
     profile) tools/gpu_session.sh \
         "prof|600|PROF_OUT=gpurun_out/prof BENCH_ARGS='--steps 2 --warmup 1 --no-cpu-baseline' tools/profile_round.sh" || exit $? ;;
     modes) tools/gpu_session.sh \

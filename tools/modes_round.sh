@@ -11,8 +11,8 @@ run c2_plain 300 --mode plain --steps 20 --no-cpu-baseline
 run c2_cvdi 300 --compositor vdi --steps 10 --no-cpu-baseline
 run c2_merge 300 --merge-bricks --steps 10 --warmup 2 --no-cpu-baseline
 run c2_host 300 --update-source host --steps 20 --no-cpu-baseline
-run c1_vdi 300 --config 1 --steps 20
-run c1_plain 300 --config 1 --mode plain --steps 20
+run c1_vdi 300 --config 1 --steps 20 --full
+run c1_plain 300 --config 1 --mode plain --steps 20 --full
 run c3 300 --config 3 --steps 10 --warmup 2 --no-cpu-baseline
 run c4 400 --config 4 --steps 10 --warmup 2 --no-cpu-baseline
 run c2_gpus2 400 --gpus 2 --steps 10 --no-cpu-baseline
