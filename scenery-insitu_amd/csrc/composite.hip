@@ -182,15 +182,10 @@ __device__ __forceinline__ void comp_search_update(CompSearch& q, int n, int S_o
     q.mid = (q.low + q.high) / 2.0f;
 }
 
-#ifndef INSITU_COMP_DEEP_WINDOW
-#define INSITU_COMP_DEEP_WINDOW 3e-3f   // search range below which the exact window spans it (as INSITU_DEEP_WINDOW)
-#endif
-
-#ifndef INSITU_COMP_MIN_WAVES
-#define INSITU_COMP_MIN_WAVES 4   // waves per SIMD of vdi_composite_kernel for V <= 8 lists (4: 128 VGPRs with spills, -0.12 ms against 3)
-#endif
+constexpr float kCompDeepWindow = 3e-3f;   // search range below which the exact window spans it (as vdi_generate.hip's kDeepWindow)
+constexpr int kCompMinWaves = 4;   // waves per SIMD of vdi_composite_kernel for V <= 8 lists (4: 128 VGPRs with spills, -0.12 ms against 3)
 template <int VMAX, bool FILTERED>
-__global__ __launch_bounds__(256, VMAX <= 8 ? INSITU_COMP_MIN_WAVES : 1) void vdi_composite_kernel(const CompositeParams P) {
+__global__ __launch_bounds__(256, VMAX <= 8 ? kCompMinWaves : 1) void vdi_composite_kernel(const CompositeParams P) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int ytiles = (P.H + 7) >> 3;
     const int tile = xcd_block((int)blockIdx.x, (int)gridDim.x) * 4 + wave;
@@ -330,13 +325,6 @@ __global__ __launch_bounds__(256, VMAX <= 8 ? INSITU_COMP_MIN_WAVES : 1) void vd
         const float cb = __builtin_fmaxf(1.0f, __builtin_fmaxf(2.0f * cmax, 2.0f * cmax * amax));
         if (FILTERED && cb < 1.0e6f) cpix = cb;   // (non-finite colours: exact decisions)
     }
-#ifdef INSITU_COMP_ABL_WALK
-    // timing ablation only (wrong results): the merging walk that fills the merge cache, no search passes
-    if (seq) {
-        oc[0] = make_float4(cpix, (float)nent, 0.0f, 0.0f);
-        return;
-    }
-#endif
 
     // the terminal sample of :277 (past the last entry): the same for every pass
     const f4 w0 = world(0.0f);
@@ -361,7 +349,7 @@ __global__ __launch_bounds__(256, VMAX <= 8 ? INSITU_COMP_MIN_WAVES : 1) void vd
             // the pass's decision thresholds (insitu_filter.h); deep in the search the exact window spans the
             // whole remaining range (vdi_generate.hip, search_thr), so the recorded interval is exact there
             Thr th = make_thr(sq_threshold(q.mid), cpix);
-            if (!q.found && q.high - q.low < INSITU_COMP_DEEP_WINDOW) {
+            if (!q.found && q.high - q.low < kCompDeepWindow) {
                 th.hi = __builtin_fmaxf(th.hi, make_thr(sq_threshold(q.high), cpix).hi);
                 th.lo = __builtin_fminf(th.lo, make_thr(sq_threshold(q.low), cpix).lo);
             }

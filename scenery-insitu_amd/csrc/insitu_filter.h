@@ -10,15 +10,13 @@
 namespace insitu {
 
 // ---- filtered supersegment test -------------------------------------------------------------
-#ifndef INSITU_HW_TRANSCENDENTALS
-#define INSITU_HW_TRANSCENDENTALS 1   // estimate's log2/exp2: 1 = hardware (default: -12 % frame time), 0 = polynomial
-#endif
 // A search pass only needs the DECISION `diff >= threshold` per sample (VDIGenerator.comp:497-529
 // reads num_terminations; the state curV never depends on the adjusted colour).  The filtered
 // form first estimates diff^2 with hardware reciprocals (v_rcp / v_rsq, <= 1 ulp) in place of
 // the three correctly rounded divisions and the square root of the exact form; when the estimate
 // is farther than a rigorous error margin from the threshold the decision is certain, otherwise
-// (and for any non-finite or extreme value) the exact contract computation decides.
+// (and for any non-finite or extreme value) the exact contract computation decides.  The estimate's
+// log2 / exp2 are the hardware instructions as well (-12 % frame time against a polynomial).
 //
 // Error budget of the estimate against the contract value.  With c = max(1, |adjusted colour|,
 // |premultiplied sample colour|): adjusted colour 2^-22 relative (rcp vs division); adjusted
@@ -88,7 +86,7 @@ __device__ __forceinline__ Thr uniform_thr(const Thr& t) {
                __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(t.lo)))};
 }
 
-// the segmentation-interval bounds from the extreme estimates of a PRE pass: lo_a = the largest
+// the segmentation-interval bounds from the extreme estimates of a filtered pass: lo_a = the largest
 // estimate of a certain non-closing decision, hi_a = the smallest of a certain closing one.  Every
 // such non-closing exact diff^2 is <= g(its estimate) <= g(lo_a) (g increasing); every such closing
 // one is >= f(its estimate) >= f(hi_a) when f(hi_a) >= 0 (all recorded estimates then lie where f
@@ -100,6 +98,5 @@ __device__ __forceinline__ float seg_lo_bound(float lo_a, float c) {
 __device__ __forceinline__ float seg_hi_bound(float hi_a, float c) {
     return (hi_a < 1.0e30f) ? hi_a - filter_margin(hi_a, c) : hi_a;
 }
-
 
 }  // namespace insitu

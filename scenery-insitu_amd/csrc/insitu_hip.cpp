@@ -1136,7 +1136,8 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
             c->dbg_pending = true;   // written to INSITU_DEBUG_RAYS at the next insitu_synchronize
         }
         HIPCHK(c, launch_vdi_sample(p, ss));
-        if (ss != sr) HIPCHK(c, hipStreamWaitEvent(sr, c->ev[5], 0));        HIPCHK(c, launch_vdi_search(p, sr));
+        if (ss != sr) HIPCHK(c, hipStreamWaitEvent(sr, c->ev[5], 0));
+        HIPCHK(c, launch_vdi_search(p, sr));
         c->search_launched = c->d_cache != nullptr;
         if (pipelined) {
             // the next frame's trigger: the search is over (mode 0), or -- the flag's safety net when no wave

@@ -20,7 +20,7 @@
 //      a ray needs no spatial coherence with its neighbours and a lane that finishes a ray
 //      takes the next one.  Rays need 1..24 passes, so per-lane work differs by more than an
 //      order of magnitude inside a tile; the queue keeps the lanes busy instead of idling
-//      until the slowest ray of their tile is done.  Late search passes (INSITU_SPEC_FROM on)
+//      until the slowest ray of their tile is done.  Late search passes (from pass kSpecFrom on)
 //      store their supersegments as they go, so a pass the search accepts at its own threshold
 //      is its own write pass.
 //
@@ -34,47 +34,6 @@
 
 namespace insitu {
 
-#ifdef INSITU_DIAG
-// diagnostics build only (tools/diag_build.sh): per-frame decision statistics printed to stderr
-__device__ unsigned long long g_diag[16];
-__device__ __forceinline__ void diag_count(int i, bool c) {
-    const unsigned long long act = __ballot(1), b = __ballot(c);
-    if ((int)(__lane_id()) == __builtin_ctzll(act)) {
-        atomicAdd(&g_diag[(i & 3) + 8 * (i >> 2)], (unsigned long long)__popcll(b));
-        atomicAdd(&g_diag[(i & 3) + 8 * (i >> 2) + 4], b ? 1ull : 0ull);
-    }
-}
-#define INSITU_DIAG_COUNT(i, c) diag_count((i), (c))
-#else
-#define INSITU_DIAG_COUNT(i, c) ((void)0)
-#endif
-// diagnostics build (-DINSITU_DIAG_TIME): per wave, the shader-clock cycles of the search loop's sections
-// (pops, regroup, replay, the round-end checks, the round-end code), summed over the waves
-#ifdef INSITU_DIAG_TIME
-__device__ unsigned long long g_dtime[8];
-#define INSITU_T_DECL                                   \
-    unsigned long long dt_acc[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull}; \
-    unsigned long long dt_mark = __builtin_readcyclecounter();
-#define INSITU_T_MARK(i)                                          \
-    {                                                             \
-        const unsigned long long t_ = __builtin_readcyclecounter(); \
-        dt_acc[i] += t_ - dt_mark;                                \
-        dt_mark = t_;                                             \
-    }
-#define INSITU_T_FLUSH()                                                               \
-    if (lane == 0)                                                                     \
-        for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&g_dtime[i_], dt_acc[i_]);
-#else
-#define INSITU_T_DECL
-#define INSITU_T_MARK(i)
-#define INSITU_T_FLUSH()
-#endif
-#if defined(INSITU_ABL_CLASSIFY2) || defined(INSITU_ABL_EST2) || defined(INSITU_ABL_LEN2) || defined(INSITU_ABL_LOGEXP2)
-// sensitivity experiments only (tools/variant_build.sh): redundant work whose result is multiplied by
-// a runtime zero, to measure what extra VALU per sample costs
-__device__ float g_abl_zero = 0.0f;
-#endif
-
 // VDIGenerator.comp:244-254
 __device__ __forceinline__ int find_z_interval_view(float z_view, float interval_size, int ncz) {
     float dist_from_front = __builtin_fabsf(z_view - (-1.0f * 0.1f));
@@ -83,18 +42,6 @@ __device__ __forceinline__ int find_z_interval_view(float z_view, float interval
     return (int)q;
 }
 
-#ifndef INSITU_SAMPLE_XCD_CHUNK
-#define INSITU_SAMPLE_XCD_CHUNK 4    // consecutive blocks one XCD runs back to back (xcd_block; round 5 at 4 waves per SIMD: 4 / 8 against 16 -0.1 / -0.05 ms, 32 +0.3)
-#endif
-#ifndef INSITU_MERGE_MIN_BLOCKS
-#define INSITU_MERGE_MIN_BLOCKS 3   // vdi_merge_kernel: waves per SIMD (A/B switch)
-#endif
-#ifndef INSITU_FINISH_MIN_BLOCKS
-#define INSITU_FINISH_MIN_BLOCKS 1  // vdi_finish_kernel: waves per SIMD asked of the compiler (A/B switch)
-#endif
-#ifndef INSITU_SAMPLE_MIN_BLOCKS
-#define INSITU_SAMPLE_MIN_BLOCKS 3   // 3 waves per SIMD (<= 168 VGPRs): measured 10.3 vs 11.4 ms at 2 waves
-#endif
 // offset (in chunks) of chunk c of a ray from its first chunk: the cache is lane-interleaved per sampling wave,
 // chunk c of lane l at base + 64 c + l, so the 64 lanes storing their chunk c write 2 KiB in one piece
 // (measured against one run per ray, -0.8 ms, and against groups of 2 or 4 chunks per lane: equal / +0.9 ms
@@ -213,14 +160,14 @@ struct SegState {
                      // the supersegment end, AccumulateVDI.comp:243-248, evaluated at the close)
     int steps_in, steps_tt;
     f4 adj, curV;
-    float lo, hi;       // segmentation interval (TRACK == 1): bounds from margins and exact values
-    float lo_a, hi_a;   // ... and the extreme estimates of precomputed-threshold decisions (PRE)
+    float lo, hi;       // segmentation interval (TRACK): the exact values of exact decisions
+    float lo_a, hi_a;   // ... and the extreme estimates of the decisions the estimate made (seg_sample_sel)
     __device__ __forceinline__ void reset() {
         nterm = 0;
         open = transparent = false;
         tt_step = 0.0f;
-        startPt = 0.0f;             // with TRACK == 2 the interval's lo in search passes (thresholds > 0)
-        endPt = __builtin_inff();   // with TRACK == 2 the interval's hi in search passes
+        startPt = 0.0f;
+        endPt = __builtin_inff();
         steps_in = steps_tt = 0;
         adj = f4{0.0f, 0.0f, 0.0f, 0.0f};
         curV = f4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -230,26 +177,6 @@ struct SegState {
     }
 };
 
-// det_log2 with its one division replaced by a hardware reciprocal (estimate only), x in [0, 1]
-__device__ __forceinline__ float approx_log2(float x) {
-    const uint32_t u = __float_as_uint(x);
-    int e = (int)((u >> 23) & 0xffu) - 127;
-    float m = __uint_as_float((u & 0x007fffffu) | 0x3f800000u);
-    const bool big = m > 1.41421354f;
-    m = big ? m * 0.5f : m;
-    e += big ? 1 : 0;
-    const float f = m - 1.0f;
-    const float sv = f * __builtin_amdgcn_rcpf(2.0f + f);
-    const float z = sv * sv;
-    float p = __builtin_fmaf(z, 0.0909090936f, 0.111111112f);
-    p = __builtin_fmaf(z, p, 0.142857149f);
-    p = __builtin_fmaf(z, p, 0.200000003f);
-    p = __builtin_fmaf(z, p, 0.333333343f);
-    const float s2 = sv + sv;
-    const float r = __builtin_fmaf(__builtin_fmaf(s2 * z, p, s2), 1.44269502f, (float)e);
-    return (x == 0.0f) ? -__builtin_inff() : r;   // x >= 2^-24 or 0 here (x = 1 - opacity)
-}
-
 // estimate of the squared supersegment difference (AccumulateVDI.comp:50-69).  The adjusted colour
 // times the adjusted opacity is formed as curV.rgb * (rcp(curV.a) * aw): the same three rounded
 // factors as (curV.rgb * rcp(curV.a)) * aw, so the same relative error budget.
@@ -257,27 +184,10 @@ __device__ __forceinline__ float approx_diff_sq(const f4& curV, int steps, const
                                                 const f4& wback, float nw) {
     const f4 jp = v4mix(wfront, wback, nw * (float)steps);
     const float dx = jp.x - wfront.x, dy = jp.y - wfront.y, dz = jp.z - wfront.z, dw = jp.w - wfront.w;
-#ifdef INSITU_ABL_LEN2
-    // timing ablation: the segment length a second time, folded in with weight 0
-    const float zz = g_abl_zero;
-    const f4 jq = v4mix(wfront, wback, nw * (float)steps + zz);
-    const float ex = jq.x - wfront.x, ey = jq.y - wfront.y, ez = jq.z - wfront.z, ew = jq.w - wfront.w;
-    const float il2 = __builtin_amdgcn_rsqf(__builtin_fmaf(ew, ew, __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex))));
-    const float inv_len = __builtin_fmaf(il2, zz, __builtin_amdgcn_rsqf(__builtin_fmaf(dw, dw, __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx)))));
-#else
     const float inv_len = __builtin_amdgcn_rsqf(__builtin_fmaf(dw, dw, __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx))));
-#endif
-#if defined(INSITU_ABL_LOGEXP2)
-    const float zz2 = g_abl_zero;
-    const float aw2 = 1.0f - __builtin_amdgcn_exp2f(inv_len * __builtin_amdgcn_logf(1.0f - curV.w + zz2));
-    const float aw = __builtin_fmaf(aw2, zz2, 1.0f - __builtin_amdgcn_exp2f(inv_len * __builtin_amdgcn_logf(1.0f - curV.w)));
-#elif INSITU_HW_TRANSCENDENTALS
     // v_log_f32 / v_exp_f32: measured exhaustively on gfx950 (tools/hw_transcendental_error.hip) at
     // < 1 ulp over the arguments they get here -- inside the error budget of filter_margin
     const float aw = 1.0f - __builtin_amdgcn_exp2f(inv_len * __builtin_amdgcn_logf(1.0f - curV.w));
-#else
-    const float aw = 1.0f - det_exp2(inv_len * approx_log2(1.0f - curV.w));
-#endif
     const float k = __builtin_amdgcn_rcpf(curV.w) * aw;
     // (ax, ay) - (bx, by) in pairs, az - bz alone: the same roundings as the scalar form
     const f2v exy = lo2(curV) * k - lo2(xv) * xv.w;
@@ -299,51 +209,22 @@ __device__ __forceinline__ float exact_diff_sq(const f4& adj, const f4& xv) {
     return sumsq3(ax - bx, ay - by, az - bz);                                          // :69 (squared)
 }
 
-// the decision `diff >= threshold` (:74), filtered or exact; sets adj when it computed it exactly.
-// bnd: the exact diff^2, or -- when the filtered estimate decided -- a bound on it in the direction
-// that matters for the segmentation interval (a lower bound for a close, an upper one otherwise);
-// with PRE the estimate itself (est = true), which seg_lo_bound / seg_hi_bound turn into bounds
-// PRE: the decision thresholds th.hi / th.lo of make_thr (uniform thresholds: scalar registers);
-// otherwise the margin is evaluated per sample (per-lane thresholds: two fewer live registers)
-template <bool FILTERED, bool PRE>
+// the decision `diff >= threshold` (:74), filtered or exact.  bnd: the exact diff^2, or -- when the
+// filtered estimate decided against the thresholds th.hi / th.lo of make_thr -- the estimate itself
+// (est = true), which seg_lo_bound / seg_hi_bound turn into bounds on the exact value
+template <bool FILTERED>
 __device__ __forceinline__ bool close_decision(const f4& curV, int steps, const f4& xv, const f4& wfront,
-                                               const f4& wback, float nw, const Thr& th, float cmag, f4& adj,
-                                               bool& have_adj, float& bnd, bool& est) {
-    if constexpr (FILTERED) {
-#ifdef INSITU_ABL_EST2
-        const float zz = g_abl_zero;
-        const float a2 = approx_diff_sq(curV, steps + (int)zz, xv, wfront, wback, nw + zz);
-        const float a = __builtin_fmaf(a2, zz, approx_diff_sq(curV, steps, xv, wfront, wback, nw));
-#else
+                                               const f4& wback, float nw, const Thr& th, float& bnd, bool& est) {
+    if constexpr (FILTERED) {   // NaN fails both tests; inf and huge estimates go to the exact path
         const float a = approx_diff_sq(curV, steps, xv, wfront, wback, nw);
-#endif
-        if constexpr (PRE) {   // NaN fails both tests; inf and huge estimates go to the exact path
-            const bool yes = a >= th.hi && a < 1.0e30f, no = a < th.lo;
-            INSITU_DIAG_COUNT(0, true);            // [0] decisions, [4] wave-level calls
-            INSITU_DIAG_COUNT(1, !yes && !no);     // [1] exact fallbacks, [5] calls with any
-            if (yes || no) {
-                bnd = a;
-                est = true;
-                return yes;
-            }
-        } else {               // NaN / inf / huge estimates fail both tests (m is NaN)
-            const float g = a - th.sq;
-            const float m = (a < 1.0e30f) ? filter_margin(a, cmag) : __builtin_nanf("");
-            INSITU_DIAG_COUNT(0, true);
-            INSITU_DIAG_COUNT(1, !(g >= m) && !(g < -m));
-            if (g >= m) {
-                bnd = a - m;
-                return true;
-            }
-            if (g < -m) {
-                bnd = a + m;
-                return false;
-            }
+        const bool yes = a >= th.hi && a < 1.0e30f, no = a < th.lo;
+        if (yes || no) {
+            bnd = a;
+            est = true;
+            return yes;
         }
     }
-    adj = exact_adjusted(curV, steps, wfront, wback, nw);
-    have_adj = true;
-    bnd = exact_diff_sq(adj, xv);
+    bnd = exact_diff_sq(exact_adjusted(curV, steps, wfront, wback, nw), xv);
     return bnd >= th.sq;
 }
 
@@ -353,54 +234,32 @@ __device__ __forceinline__ bool close_decision(const f4& curV, int steps, const 
 // a supersegment opens (at stp, AccumulateVDI.comp:214-217) and when it closes (at the step after
 // its last non-transparent sample, AccumulateVDI.comp:243-248 -- the same `step + nw` the loop
 // increment computes, so the same bits as evaluating it at every sample).
-// emit(start, end, adjusted colour, steps) runs for every supersegment that closes; with FILTERED
-// the adjusted colour handed to emit is exact only when want_adj is set (the write pass).  With
-// DEFER the colour handed over is the raw accumulated curV and steps its step count, from which
+// emit(start, end, adjusted colour, steps) runs for every supersegment that closes.  With DEFER the
+// colour handed over is the raw accumulated curV and steps its step count, from which
 // vdi_finish_kernel computes the adjusted colour (AccumulateVDI.comp:50-54) afterwards.
-// th.sq = sq_threshold(threshold): `diff >= threshold` is tested as `diff^2 >= th.sq` (th: make_thr).
-// TRACK: 0 no segmentation interval, 1 in s.lo / s.hi, 2 in s.startPt / s.endPt while !want_adj
-// (a search pass of vdi_search_kernel needs no supersegment positions: no extra registers).
-template <bool FILTERED = false, int TRACK = 0, bool DEFER = false, bool PRE = false, class NdcOf, class Emit>
+// th.sq = sq_threshold(threshold): `diff >= threshold` is tested as `diff^2 >= th.sq`, every decision
+// exact (the filtered form of the search kernel's replay is seg_sample_sel).
+// TRACK: the segmentation interval of the pass is kept in s.lo / s.hi.
+template <bool TRACK = false, bool DEFER = false, class NdcOf, class Emit>
 __device__ __forceinline__ void seg_sample(SegState& s, const f4 xv, const float wv, const float stp, NdcOf ndc_of,
                                            const bool last, const Thr& th, const f4& wfront,
-                                           const f4& wback, const float nw, const float cmag, Emit emit,
-                                           const bool want_adj = true) {
+                                           const f4& wback, const float nw, Emit emit) {
     s.transparent = false;
     if (!(xv.x > -0.5f || last)) return;                                             // :12
     if (wv <= 0.0f) s.transparent = true;                                            // :24-26
-    const bool positions = TRACK != 2 || want_adj;
     if (s.open) {                                                                    // :34-91
-        bool have_adj = false;
-        float bnd;
-        bool est = false;
-        const bool close = close_decision<FILTERED, PRE>(s.curV, s.steps_in, xv, wfront, wback, nw, th, cmag, s.adj,
-                                                         have_adj, bnd, est);
-        if constexpr (TRACK == 1) {
-            if (PRE && est) {
-                if (close) s.hi_a = __builtin_fminf(s.hi_a, bnd);
-                else s.lo_a = __builtin_fmaxf(s.lo_a, bnd);
-            } else {
-                if (close) s.hi = __builtin_fminf(s.hi, bnd);
-                else s.lo = __builtin_fmaxf(s.lo, bnd);
-            }
-        }
-        if constexpr (TRACK == 2) {
-            if (!want_adj) {
-                if (PRE && est) {
-                    if (close) s.hi_a = __builtin_fminf(s.hi_a, bnd);
-                    else s.lo_a = __builtin_fmaxf(s.lo_a, bnd);
-                } else {
-                    if (close) s.endPt = __builtin_fminf(s.endPt, bnd);
-                    else s.startPt = __builtin_fmaxf(s.startPt, bnd);
-                }
-            }
+        s.adj = exact_adjusted(s.curV, s.steps_in, wfront, wback, nw);
+        const float bnd = exact_diff_sq(s.adj, xv);
+        const bool close = bnd >= th.sq;                                             // :74
+        if constexpr (TRACK) {
+            if (close) s.hi = __builtin_fminf(s.hi, bnd);
+            else s.lo = __builtin_fmaxf(s.lo, bnd);
         }
         if (close) {
-            if (!DEFER && FILTERED && want_adj && !have_adj) s.adj = exact_adjusted(s.curV, s.steps_in, wfront, wback, nw);
             const int steps = s.steps_in;
             s.nterm++;
             s.open = false;
-            if (positions) s.endPt = ndc_of(s.tt_step + nw);                        // :126 (ndc_step)
+            s.endPt = ndc_of(s.tt_step + nw);                                        // :126 (ndc_step)
             s.steps_in = 0;
             s.steps_tt = 0;
             emit(s.startPt, s.endPt, DEFER ? s.curV : s.adj, steps);                // :132-180
@@ -408,7 +267,7 @@ __device__ __forceinline__ void seg_sample(SegState& s, const f4 xv, const float
     }
     if (!s.open && !s.transparent) {                                                 // :185-221
         s.open = true;
-        if (positions) s.startPt = ndc_of(stp);
+        s.startPt = ndc_of(stp);
         s.curV = f4{0.0f, 0.0f, 0.0f, 0.0f};
     }
     if (s.open) {                                                                    // :225-251
@@ -416,46 +275,38 @@ __device__ __forceinline__ void seg_sample(SegState& s, const f4 xv, const float
         s.steps_in++;
         if (!s.transparent) {
             s.steps_tt = s.steps_in;
-            if (positions) s.tt_step = stp;                                          // ndc_step at :243-248
+            s.tt_step = stp;                                                         // ndc_step at :243-248
         }
     }
     if (last && s.open) {                                                            // :257-335
-        if (!DEFER && (!FILTERED || want_adj)) s.adj = exact_adjusted(s.curV, s.steps_tt, wfront, wback, nw);
+        if (!DEFER) s.adj = exact_adjusted(s.curV, s.steps_tt, wfront, wback, nw);
         s.nterm++;
         s.open = false;
-        if (positions) s.endPt = ndc_of(s.tt_step + nw);                            // :299
+        s.endPt = ndc_of(s.tt_step + nw);                                            // :299
         s.steps_in = 0;
         emit(s.startPt, s.endPt, DEFER ? s.curV : s.adj, s.steps_tt);
     }
 }
 
-// seg_sample<true, 1, true, PRE> (the search kernel's replay: filtered decisions, segmentation interval in
-// s.lo / s.hi, deferred colours, supersegment boundaries as ray parameters) with the state updates written as
-// selects: the same float operations on the same operands, so the same states and the same stores.  Only the
+// The search kernel's filtered replay: seg_sample<true, true> (segmentation interval, deferred colours,
+// supersegment boundaries as ray parameters) with the decisions of close_decision<true> -- the estimate
+// against th.hi / th.lo, the exact value only between them -- and the state updates written as selects:
+// the same float operations on the same operands, so the same states and the same stores.  Only the
 // rare paths branch -- the exact decision (0.01 % of the decisions) and the stores of storing lanes -- and the
-// estimate is computed for every lane of the wave (in the branching form some lane of the wave needs it at
+// estimate is computed for every lane of the wave (in a branching form some lane of the wave needs it at
 // almost every sample).  `on` gates the whole sample (a lane past the end of its pass: no state change).
-template <bool PRE, class Emit>
+template <class Emit>
 __device__ __forceinline__ void seg_sample_sel(SegState& s, const f4 xv, const float wv, const float stp, const bool on,
                                                const bool last, const Thr& th, const f4& wfront, const f4& wback,
-                                               const float nw, const float cmag, Emit emit, const bool store) {
+                                               const float nw, Emit emit, const bool store) {
     const bool v = on && (xv.x > -0.5f || last);                                    // :12
     const bool tr = wv <= 0.0f;                                                      // :24-26
     const bool o = v && s.open;                                                      // :34-91
     const float a = approx_diff_sq(s.curV, s.steps_in, xv, wfront, wback, nw);
-    bool close, est;
-    if constexpr (PRE) {   // NaN fails both tests; inf and huge estimates go to the exact path
-        const bool yes = a >= th.hi && a < 1.0e30f, no = a < th.lo;
-        close = yes;
-        est = yes || no;
-    } else {
-        const float g = a - th.sq;
-        const float m = (a < 1.0e30f) ? filter_margin(a, cmag) : __builtin_nanf("");
-        close = g >= m;
-        est = close || g < -m;
-    }
-    INSITU_DIAG_COUNT(0, o);
-    INSITU_DIAG_COUNT(1, o && !est);
+    // NaN fails both tests; inf and huge estimates go to the exact path
+    const bool yes = a >= th.hi && a < 1.0e30f, no = a < th.lo;
+    bool close = yes;
+    const bool est = yes || no;
     float bnd = a;
     if (o && !est) {   // exact decision (close_decision's fallback)
         const f4 adj = exact_adjusted(s.curV, s.steps_in, wfront, wback, nw);
@@ -465,16 +316,9 @@ __device__ __forceinline__ void seg_sample_sel(SegState& s, const f4 xv, const f
         else s.lo = __builtin_fmaxf(s.lo, bnd);
     }
     close = close && o;
-    if constexpr (PRE) {   // TRACK == 1 bounds of the estimate-decided samples
-        const bool eu = o && est;
-        s.hi_a = __builtin_fminf(s.hi_a, (eu && close) ? a : __builtin_inff());
-        s.lo_a = __builtin_fmaxf(s.lo_a, (eu && !close) ? a : -1.0f);   // (lo_a >= -1 always)
-    } else {
-        const bool eu = o && est;
-        const float m = filter_margin(a, cmag);
-        s.hi = __builtin_fminf(s.hi, (eu && close) ? a - m : __builtin_inff());
-        s.lo = __builtin_fmaxf(s.lo, (eu && !close) ? a + m : 0.0f);   // (lo >= 0 always)
-    }
+    const bool eu = o && est;   // the extreme estimates of the estimate-decided samples
+    s.hi_a = __builtin_fminf(s.hi_a, (eu && close) ? a : __builtin_inff());
+    s.lo_a = __builtin_fmaxf(s.lo_a, (eu && !close) ? a : -1.0f);   // (lo_a >= -1 always)
     if (close && store) emit(s.startPt, s.tt_step + nw, s.curV, s.steps_in);       // :126, :132-180
     s.nterm += close ? 1 : 0;
     const bool open1 = s.open && !close;
@@ -499,65 +343,12 @@ __device__ __forceinline__ void seg_sample_sel(SegState& s, const f4 xv, const f
     s.steps_in = lc ? 0 : s.steps_in;
 }
 
-// The supersegment counter of one raymarch pass without the supersegments themselves: the
-// decisions of seg_sample (same float operations, same order) but only `nterm` is kept -- what a
-// search pass needs (VDIGenerator.comp:497-529 reads num_terminations only).
-struct CountState {
-    f4 curV;
-    int steps_in, nterm;
-    bool open;
-    float lo, hi, lo_a, hi_a;   // segmentation interval (see SegState)
-    __device__ __forceinline__ void reset() {
-        curV = f4{0.0f, 0.0f, 0.0f, 0.0f};
-        steps_in = nterm = 0;
-        open = false;
-        lo = 0.0f;
-        lo_a = -1.0f;
-        hi = hi_a = __builtin_inff();
-    }
-};
-
-template <bool FILTERED, bool PRE>
-__device__ __forceinline__ void count_sample(CountState& s, const f4 xv, const float wv, const bool last,
-                                             const Thr& th, const f4& wfront, const f4& wback,
-                                             const float nw, const float cmag) {
-    if (!(xv.x > -0.5f || last)) return;
-    const bool transparent = wv <= 0.0f;
-    if (s.open) {
-        f4 adj;
-        bool have_adj = false;
-        float bnd;
-        bool est = false;
-        if (close_decision<FILTERED, PRE>(s.curV, s.steps_in, xv, wfront, wback, nw, th, cmag, adj, have_adj, bnd, est)) {
-            if (est) s.hi_a = __builtin_fminf(s.hi_a, bnd);
-            else s.hi = __builtin_fminf(s.hi, bnd);
-            s.nterm++;
-            s.open = false;
-            s.steps_in = 0;
-        } else {
-            if (est) s.lo_a = __builtin_fmaxf(s.lo_a, bnd);
-            else s.lo = __builtin_fmaxf(s.lo, bnd);
-        }
-    }
-    if (!s.open && !transparent) {
-        s.open = true;
-        s.curV = f4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
-    if (s.open) {
-        s.curV = accumulate(s.curV, xv, wv);
-        s.steps_in++;
-    }
-    if (last && s.open) {
-        s.nterm++;
-        s.open = false;
-    }
-}
-
-// Pass 1 and the spine counts of vdi_sample_kernel / vdi_merge_kernel: count_sample's state with the bounds of
-// the exact decisions (lo, hi: changed by 0.01 % of the decisions) kept in LDS -- bnd[0] = lo, bnd[256] = hi,
-// the lane's slots -- instead of two VGPRs per threshold (the kernel then fits 4 waves per SIMD).  The same
-// decisions and values as count_sample.  (Pass 1 needs only its count and segmentation interval: count_sample
-// makes the same decisions and counts as seg_sample with deferred colours.)
+// Pass 1 and the spine counts of vdi_sample_kernel / vdi_merge_kernel: the supersegment counter of one raymarch
+// pass without the supersegments themselves -- the decisions of seg_sample (same float operations, same order)
+// but only `nterm` and the segmentation interval are kept, which is what a search pass needs
+// (VDIGenerator.comp:497-529 reads num_terminations only).  The bounds of the exact decisions (lo, hi: changed
+// by 0.01 % of the decisions) live in LDS -- bnd[0] = lo, bnd[256] = hi, the lane's slots -- instead of two
+// VGPRs per threshold (the kernel then fits 4 waves per SIMD); lo_a, hi_a as in SegState.
 struct CountStateL {
     f4 curV;
     int steps_in, nterm;
@@ -572,18 +363,15 @@ struct CountStateL {
     }
 };
 
-template <bool FILTERED, bool PRE>
+template <bool FILTERED>
 __device__ __forceinline__ void count_sample_l(CountStateL& s, float* bnd, const f4 xv, const float wv, const bool last,
-                                               const Thr& th, const f4& wfront, const f4& wback, const float nw,
-                                               const float cmag) {
+                                               const Thr& th, const f4& wfront, const f4& wback, const float nw) {
     if (!(xv.x > -0.5f || last)) return;
     const bool transparent = wv <= 0.0f;
     if (s.open) {
-        f4 adj;
-        bool have_adj = false;
         float b;
         bool est = false;
-        if (close_decision<FILTERED, PRE>(s.curV, s.steps_in, xv, wfront, wback, nw, th, cmag, adj, have_adj, b, est)) {
+        if (close_decision<FILTERED>(s.curV, s.steps_in, xv, wfront, wback, nw, th, b, est)) {
             if (est) s.hi_a = __builtin_fminf(s.hi_a, b);
             else bnd[256] = __builtin_fminf(bnd[256], b);
             s.nterm++;
@@ -795,7 +583,7 @@ __device__ void vdi_march(const VdiGenParams& P, const BrickDesc& brick, uint32_
                 }
             };
             march_pass<DT>(P, brick, s_tf, s_cm, R, [&](int, float, const f4& x, float w, float stp, bool last) {
-                seg_sample(st, x, w, stp, ndc_of, last, th, R.wfront, R.wback, nw, P.xfer.cmag, emit);
+                seg_sample(st, x, w, stp, ndc_of, last, th, R.wfront, R.wback, nw, emit);
                 // a search pass that has closed more than S supersegments is decided
                 // (:511-514 only asks n > S, or n == 0): skip its remaining samples
                 return write || st.nterm <= S;
@@ -902,7 +690,7 @@ __device__ void merge_search_in_place(const VdiGenParams& P, const float* s_tf, 
                     float w = 0.0f;
                     if (x.x > -0.5f || last)
                         w = adjust_opacity(x.w, len4(wpos.x - wprev.x, wpos.y - wprev.y, wpos.z - wprev.z, wpos.w - wprev.w));
-                    seg_sample(st, x, w, step, ndc_of, last, th, R.wfront, R.wback, nw, P.xfer.cmag, emit);
+                    seg_sample(st, x, w, step, ndc_of, last, th, R.wfront, R.wback, nw, emit);
                     // a search pass that has closed more than S supersegments is decided (:511-514)
                     if (!write && st.nterm > S) {
                         decided = true;
@@ -974,15 +762,7 @@ __device__ __forceinline__ void march_multi(const VdiGenParams& P, const float* 
         step = step + nw;
     }
 }
-#ifndef INSITU_PASS1_PRE
-#define INSITU_PASS1_PRE 1    // pass 1 and the spine counts decide with make_thr's thresholds (A/B switch)
-#endif
-#ifndef INSITU_PASS1_STOP
-#define INSITU_PASS1_STOP 1   // pass 1 and the spine counts stop at S + 1 closes (A/B switch)
-#endif
-#ifndef INSITU_SPEC_LEVELS
-#define INSITU_SPEC_LEVELS 4   // search levels pass 1 counts along the "fewer than S - delta" spine (0..5)
-#endif
+
 // Stores of chunk c (counted from the ray's first chunk) of one ray: 32 bytes {LUT coordinate x4,
 // adjusted opacity x4}.  at(c) is the chunk's address (merged volumes' step indices go beside it).
 struct PlainChunkStore {   // the two-kernel generator: the search kernel reads the cache after this launch
@@ -1014,6 +794,8 @@ struct MergedChunkStore {
     }
 };
 
+constexpr int kSpecLevels = 4;   // search levels pass 1 counts along the "fewer than S - delta" spine (1..5)
+
 // Pass 1 (threshold 1e-4) of a ray with cache space, and the queue record of the rest of its search
 // (VDIGenerator.comp:380-539).  march(sample_fn, flush_fn) runs the raymarch pass: march_pass over a
 // brick, or march_multi over the volumes of a merged VDI (MERGED: each sample's step index is cached
@@ -1032,7 +814,7 @@ __device__ bool first_pass_impl(const VdiGenParams& P, const f4& wfront, const f
     // the chunk being filled {coord x4, opacity x4}; merged volumes (paired slots, MergedChunkStore): the pair
     // being filled {coord x4, opacity x4} x 2 and its 8 step indices (u16), stored as one 128-byte line
     constexpr bool PAIRS = MERGED;
-    float* const chk = p1 + 512 * (INSITU_SPEC_LEVELS + 1) + (PAIRS ? 20 : 8) * tid;
+    float* const chk = p1 + 512 * (kSpecLevels + 1) + (PAIRS ? 20 : 8) * tid;
     CountStateL st;   // pass 1 (level 0)
     st.reset();
     // The same pass also counts the supersegments at the thresholds the search tries next: the
@@ -1040,11 +822,12 @@ __device__ bool first_pass_impl(const VdiGenParams& P, const f4& wfront, const f
     // state machines.  They follow the tree's "n < S - delta" spine (high = mid at every level:
     // 0.866, 0.433, 0.217, 0.108 ...), the path every searched ray takes for its first three levels
     // and 84 % of them for four (tools/checkpoint_study.py, brick 7 of the bench): a searching ray
-    // enters the search kernel INSITU_SPEC_LEVELS passes further on.
+    // enters the search kernel kSpecLevels passes further on.
     const float root_mid = (0.0001f + 1.732f) / 2.0f;                                // :519-527
-    constexpr int K = INSITU_SPEC_LEVELS;
-    CountStateL cs[K > 0 ? K : 1];
-    Thr tk[K > 0 ? K : 1];
+    constexpr int K = kSpecLevels;
+    static_assert(kSpecLevels >= 1);
+    CountStateL cs[K];
+    Thr tk[K];
 #pragma unroll
     for (int l = 0, node = 0; l < K; ++l, node = 2 * node + 2) {
         cs[l].reset();
@@ -1096,20 +879,13 @@ __device__ bool first_pass_impl(const VdiGenParams& P, const f4& wfront, const f
         // search kernel's passes do.  Its segmentation interval then bounds the decisions of the
         // samples seen so far, which is all the "n > S" conclusion rests on (every threshold in it
         // closes the same S + 1 supersegments over that prefix).
-#ifdef INSITU_ABL_NOPASS1
-        if (false)   // ablation (timing only, wrong results): sampling and cache fill without pass 1
-#else
-        if (!INSITU_PASS1_STOP || st.nterm <= S)
-#endif
-            count_sample_l<FILTERED, INSITU_PASS1_PRE>(st, bl, x, w, last, th1, wfront, wback, nw, P.xfer.cmag);
+        if (st.nterm <= S) count_sample_l<FILTERED>(st, bl, x, w, last, th1, wfront, wback, nw);
 #pragma unroll
         for (int l = 0; l < K; ++l)
-            if (!INSITU_PASS1_STOP || cs[l].nterm <= S)
-                count_sample_l<FILTERED, INSITU_PASS1_PRE>(cs[l], bl + 512 * (l + 1), x, w, last, tk[l], wfront, wback, nw,
-                                                          P.xfer.cmag);
+            if (cs[l].nterm <= S)
+                count_sample_l<FILTERED>(cs[l], bl + 512 * (l + 1), x, w, last, tk[l], wfront, wback, nw);
         return true;   // the cache needs every sample
     }, [&] {
-#ifndef INSITU_ABL_NOSTORE
         if (store_chunk) {
             const float4 bc = *reinterpret_cast<const float4*>(chk), bw = *reinterpret_cast<const float4*>(chk + 4);
             if constexpr (PAIRS) {
@@ -1119,7 +895,6 @@ __device__ bool first_pass_impl(const VdiGenParams& P, const f4& wfront, const f
                 store_fn((uint32_t)(k - 1) >> 2, bc, bw);
             }
         }
-#endif
         store_chunk = false;
     });
     if constexpr (MERGED) {
@@ -1206,8 +981,10 @@ __device__ __forceinline__ bool vdi_first_pass(const VdiGenParams& P, const Bric
 // samples and their step indices cached, the ray queued for vdi_search_kernel<., true> -- the
 // sampling/search split of the brick rays.  A ray whose samples outgrow its cache space (estimated
 // from its volume intervals) is searched in place by re-sampling, as are rays without cache space.
+constexpr int kSampleXcdChunk = 4;   // consecutive blocks one XCD runs back to back (xcd_block; round 5 at 4 waves per SIMD: 4 / 8 against 16 -0.1 / -0.05 ms, 32 +0.3)
+constexpr int kMergeMinBlocks = 3;   // vdi_merge_kernel: waves per SIMD
 template <int DT, bool FILTERED>
-__global__ __launch_bounds__(256, INSITU_MERGE_MIN_BLOCKS) void vdi_merge_kernel(const VdiGenParams P) {
+__global__ __launch_bounds__(256, kMergeMinBlocks) void vdi_merge_kernel(const VdiGenParams P) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     float4* s_cm = smem;
     float* s_tf = reinterpret_cast<float*>(smem + lut_cm_slots(P.xfer.n_cm));
@@ -1216,7 +993,7 @@ __global__ __launch_bounds__(256, INSITU_MERGE_MIN_BLOCKS) void vdi_merge_kernel
     int tile = xcd_block((int)blockIdx.x, (int)gridDim.x) * 4 + wave;
     if (P.tile_ids) {   // longest tiles first (vdi_tile_len_kernel + sort), as the brick sampling kernel
         const int ntiles = P.ytiles * P.nstrips * P.strip_tiles;
-        const int j = xcd_block((int)blockIdx.x, (int)gridDim.x, INSITU_SAMPLE_XCD_CHUNK) * 4 + wave;
+        const int j = xcd_block((int)blockIdx.x, (int)gridDim.x, kSampleXcdChunk) * 4 + wave;
         tile = j < ntiles ? (int)P.tile_ids[ntiles + j] : 4 * ntiles;   // sorted half (past the end: invalid)
     }
     const int yt = tile % P.ytiles, ct = tile / P.ytiles;
@@ -1287,9 +1064,7 @@ __global__ __launch_bounds__(256, INSITU_MERGE_MIN_BLOCKS) void vdi_merge_kernel
     if (pend) P.queue[q0 + (uint32_t)__popcll(mp & ((1ull << lane) - 1ull))] = pr;
 }
 
-#ifndef INSITU_TILE_CLASS_SHIFT
-#define INSITU_TILE_CLASS_SHIFT 4   // length classes of 2^4 = 16 samples (measured 2..8: 3-4 best)
-#endif
+constexpr int kTileClassShift = 4;   // length classes of 2^4 = 16 samples (measured 2..8: 3-4 best)
 // The sort key of every (brick, tile) for the longest-tiles-first order: the longest ray of the tile's
 // SUPER-TILE (P.super_tile^2 tiles, 1 = the tile itself) in 16-sample classes (high byte), then the
 // super-tile's position and the tile's place in it (so a class keeps the spatial order, and the tiles of a
@@ -1339,7 +1114,7 @@ __global__ __launch_bounds__(1024) void vdi_tile_len_kernel(const VdiGenParams P
         // < 2^24 (host-checked for sup <= 4); sup = 1: spos = pos
         const uint32_t spos = (((uint32_t)b * (uint32_t)nsx + (uint32_t)sx) * (uint32_t)nsy + (uint32_t)sy) * (uint32_t)sup2 +
                               (uint32_t)sub;
-        const uint32_t cls = (uint32_t)min(s_max[sl] >> INSITU_TILE_CLASS_SHIFT, 255);
+        const uint32_t cls = (uint32_t)min(s_max[sl] >> kTileClassShift, 255);
         P.tile_keys[pos] = (cls << 24) | (0xffffffu - spos);
         P.tile_ids[pos] = pos;
     }
@@ -1376,7 +1151,7 @@ __global__ __launch_bounds__(256) void vdi_tile_len_sub_kernel(const VdiGenParam
     for (int o = 8; o > 0; o >>= 1) steps = max(steps, __shfl_xor(steps, o));
     if (s == 0 && tile < ntiles) {
         const uint32_t pos = (uint32_t)b * (uint32_t)ntiles + (uint32_t)tile;
-        const uint32_t cls = (uint32_t)min(steps >> INSITU_TILE_CLASS_SHIFT, 255);
+        const uint32_t cls = (uint32_t)min(steps >> kTileClassShift, 255);
         P.tile_keys[pos] = (cls << 24) | (0xffffffu - pos);
         P.tile_ids[pos] = pos;
     }
@@ -1440,9 +1215,7 @@ __device__ __forceinline__ void sample_tile(const VdiGenParams& P, const float* 
             pr.b = (uint32_t)b;
             pr.chunk = chunk;
         } else {
-#ifndef INSITU_ABL_NOMARCH
             vdi_march<DT>(P, brick, oct, pas, pnd, s_tf, s_cm, R, o);
-#endif
         }
     }
     // append the unfinished rays to the search queue (one atomic per wave and class): long rays
@@ -1462,8 +1235,9 @@ __device__ __forceinline__ void sample_tile(const VdiGenParams& P, const float* 
     }
 }
 
+constexpr int kSampleMinBlocks = 3;   // 3 waves per SIMD (<= 168 VGPRs): measured 10.3 vs 11.4 ms at 2 waves
 template <int DT, bool FILTERED>
-__global__ __launch_bounds__(256, INSITU_SAMPLE_MIN_BLOCKS) void vdi_sample_kernel(const VdiGenParams P) {
+__global__ __launch_bounds__(256, kSampleMinBlocks) void vdi_sample_kernel(const VdiGenParams P) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     float4* s_cm = smem;
     float* s_tf = reinterpret_cast<float*>(smem + lut_cm_slots(P.xfer.n_cm));
@@ -1473,7 +1247,7 @@ __global__ __launch_bounds__(256, INSITU_SAMPLE_MIN_BLOCKS) void vdi_sample_kern
     // XCD-aware order over all (brick, tile-block) pairs: each XCD walks a contiguous range, i.e.
     // mostly one brick and neighbouring tiles, so its L2 holds the brick region its rays sample
     const int lin = (int)(blockIdx.y * gridDim.x + blockIdx.x);
-    const int logical = xcd_block(lin, (int)(gridDim.x * gridDim.y), INSITU_SAMPLE_XCD_CHUNK);
+    const int logical = xcd_block(lin, (int)(gridDim.x * gridDim.y), kSampleXcdChunk);
     int b, tile;
     if (P.tile_ids) {
         // longest tiles first (vdi_tile_len_kernel + sort): the launch ends with short tiles, not
@@ -1504,33 +1278,23 @@ __global__ __launch_bounds__(256, INSITU_SAMPLE_MIN_BLOCKS) void vdi_sample_kern
 // thresholds of the next d levels of the binary search tree; walking the tree with those counts
 // lands exactly where d sequential passes would (same thresholds, same decisions), so a ray needs
 // ceil(levels / d) rounds instead of one pass per level.  G = 1 is the plain sequential search.
-#ifndef INSITU_SPEC_WRITE
-#define INSITU_SPEC_WRITE 1   // search passes of a group's root store their supersegments: an accepted pass needs no write pass
-#endif
-#ifndef INSITU_SPEC_FROM
-#define INSITU_SPEC_FROM 8    // ... from this pass number on: later passes are accepted more often (measured 7..9)
-#endif
-#ifndef INSITU_SPEC_FROM_GROUP
-#define INSITU_SPEC_FROM_GROUP 7   // ... with tree groups (short queues: the per-GPU share of many GPUs)
-#endif
-#ifndef INSITU_SEARCH_MIN_WAVES
-#define INSITU_SEARCH_MIN_WAVES 3    // 3 waves per SIMD: <= 168 VGPRs (hang guard)
-#endif
+//
+// Search passes of a group's root store their supersegments, so an accepted pass needs no write pass ...
+constexpr int kSpecFrom = 8;        // ... from this pass number on: later passes are accepted more often (measured 7..9)
+constexpr int kSpecFromGroup = 7;   // ... with tree groups (short queues: the per-GPU share of many GPUs)
+constexpr int kSearchMinWaves = 3;  // 3 waves per SIMD: <= 168 VGPRs (hang guard)
 constexpr int kMaxSearchDepth = 6;
-#ifndef INSITU_REGROUP_MAX_DEPTH
-#define INSITU_REGROUP_MAX_DEPTH 4   // deepest tree a regroup forms (15 lanes per ray)
-#endif
-constexpr int kMaxRegroupDepth = INSITU_REGROUP_MAX_DEPTH;
+constexpr int kMaxRegroupDepth = 4;   // deepest tree a regroup forms (15 lanes per ray)
 
 // the sampling kernels' LDS: the LUTs, then the pass-1 area of first_pass_impl (per lane the exact-decision bounds
 // of pass 1 and the spine levels, and the chunk being filled)
-constexpr int kP1LdsFloats = 512 * (INSITU_SPEC_LEVELS + 1) + 8 * 256;
+constexpr int kP1LdsFloats = 512 * (kSpecLevels + 1) + 8 * 256;
 __host__ __device__ __forceinline__ size_t sample_lds_bytes(int n_tf, int n_cm) {
     return lut_lds_bytes(n_tf, n_cm) + (size_t)kP1LdsFloats * 4;
 }
 // vdi_merge_kernel: the same with the pair staging of paired merged slots (20 words per lane)
 __host__ __device__ __forceinline__ size_t merge_lds_bytes(int n_tf, int n_cm) {
-    return lut_lds_bytes(n_tf, n_cm) + (size_t)(512 * (INSITU_SPEC_LEVELS + 1) + 20 * 256) * 4;
+    return lut_lds_bytes(n_tf, n_cm) + (size_t)(512 * (kSpecLevels + 1) + 20 * 256) * 4;
 }
 
 __host__ __device__ __forceinline__ size_t search_lds_bytes(int n_tf, int n_cm) {
@@ -1540,29 +1304,18 @@ __host__ __device__ __forceinline__ size_t search_lds_bytes(int n_tf, int n_cm) 
     return lut_lds_bytes(n_tf, n_cm) + 4 * 256 * 16 + 256 * 4 + 2 * 16 + 256 * 4 + 256 * 8 + 256 * 8;
 }
 
-#ifndef INSITU_GROUP_BATCH
-#define INSITU_GROUP_BATCH 6   // tree-group mode: lanes that must have ended a round before the round-end code runs (one brick per GPU: 6.71 -> 6.49 ms)
-#endif
-#ifndef INSITU_SEL_REPLAY
-#define INSITU_SEL_REPLAY 1   // the search replay's state updates as selects (seg_sample_sel; A/B switch)
-#endif
-#ifndef INSITU_SEARCH_PRE
-#define INSITU_SEARCH_PRE 1   // search passes decide with make_thr's thresholds (A/B switch)
-#endif
-#ifndef INSITU_DEEP_WINDOW
-#define INSITU_DEEP_WINDOW 3e-3f   // search range (high - low) below which the exact window spans it (measured: 1e-4..1e-1)
-#endif
-// The decision thresholds of a search pass.  Deep in the search (high - low below
-// INSITU_DEEP_WINDOW) every threshold still to come lies in (low, high), a few ulps to a few 1e-4
+constexpr int kGroupBatch = 6;   // tree-group mode: lanes that must have ended a round before the round-end code runs (one brick per GPU: 6.71 -> 6.49 ms)
+constexpr float kDeepWindow = 3e-3f;   // search range (high - low) below which the exact window spans it (measured: 1e-4..1e-1)
+// The decision thresholds of a search pass (make_thr's).  Deep in the search (high - low below
+// kDeepWindow) every threshold still to come lies in (low, high), a few ulps to a few 1e-4
 // apart, while the filtered decisions' bounds are loose by the margin (~1e-5 relative): the
 // segmentation interval of a pass then cannot cover the next threshold and free_walk replays passes
 // that make the same decisions.  There the exact window spans the whole remaining range: samples
 // whose estimate could lie on either side of ANY remaining threshold take the exact path, the
 // others are certain for all of them, so the pass's interval is exact across the range.
 __device__ __forceinline__ Thr search_thr(float t_sq, float c, const Search& q) {
-    if (!INSITU_SEARCH_PRE) return Thr{t_sq, 0.0f, 0.0f};
     Thr r = make_thr(t_sq, c);
-    if (!q.found && q.high - q.low < INSITU_DEEP_WINDOW) {
+    if (!q.found && q.high - q.low < kDeepWindow) {
         r.hi = __builtin_fmaxf(r.hi, make_thr(sq_threshold(q.high), c).hi);
         r.lo = __builtin_fminf(r.lo, make_thr(sq_threshold(q.low), c).lo);
     }
@@ -1622,7 +1375,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
     int node = lane % G, gbase = lane - node;
     bool member = lane < (64 / G) * G;
     bool leader_lane = member && node == 0;
-    int spec_from = G == 1 ? INSITU_SPEC_FROM : INSITU_SPEC_FROM_GROUP;   // INSITU_SPEC_WRITE
+    int spec_from = G == 1 ? kSpecFrom : kSpecFromGroup;
     // the LDS slots of the lane's ray (chunk 0, search intervals, diagnostics): its group leader's at the pop,
     // kept when a regroup moves the ray to other lanes
     int home = tid;
@@ -1644,16 +1397,13 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
     size_t e0 = 0;                   // entry of slot 0 of the pixel's output block (ray_out)
     const size_t slot_stride = (size_t)P.H * 8;
     Search q{};                      // root of the group's current round (identical in all its lanes)
-    Thr th{};                        // this lane's tree node threshold (or the final one); margin per sample
+    Thr th{};                        // the decision thresholds of this lane's tree node (or of the final pass)
     SegState st;
     st.reset();
     int nseg = 0, k = 0, n = 0, nchunks = 1, pre_chunk = 0;
     uint32_t cur_step = 0;           // MERGED: the step index stp belongs to
     uint2 s4{}, ps4{};               // MERGED: step indices of the chunk being replayed / the next one
     float stp = 0.0f;                // ray parameter of the sample being replayed (write pass positions)
-#ifdef INSITU_DEBUG_REPLAYS
-    uint32_t dbg_rounds = 0;         // diagnostics build: rounds (replays) of the ray, recorded with P.debug_rays
-#endif
     float4 c4{}, w4{};               // chunk being replayed
     float4 pc4{}, pw4{};             // next chunk, loaded one loop trip ahead
     auto ndc_of = [](float t) { return t; };   // write passes store ray parameters (vdi_finish_kernel)
@@ -1697,9 +1447,6 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
         if (P.debug_rays) {
             s_dbg_slot[home] = r;
             s_dbg_t0[home] = wall_clock64();
-#ifdef INSITU_DEBUG_REPLAYS
-            dbg_rounds = 1;
-#endif
         }
     };
     // every wave leaves the loop: when the queue is drained and its lanes are idle, or -- never
@@ -1711,9 +1458,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
     // wait at the top of every trip cost ~40 cycles each)
     const unsigned long long t_end = wall_clock64() + 1000000000ull;
     uint32_t trips = 0u;
-    INSITU_T_DECL
     for (;;) {
-        INSITU_T_MARK(4)   // (the round-end code, and the checks of trips that continued after the replay)
         if ((++trips & 255u) == 0u && wall_clock64() > t_end) {
             if (lane == 0) atomicOr(&ctr->fault, 1u);
             break;
@@ -1725,7 +1470,6 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
             uint32_t base = 0;
             if (lane == first) base = atomicAdd(&ctr->queue_head, cnt);
             base = __shfl(base, first);
-            INSITU_T_MARK(5)   // (the claim: ballot, atomic, broadcast)
             if (base + cnt >= qlen) {
                 // pipelined frames: the claim that drains the queue (one wave's) starts the next frame's first pass
                 // (the flag's address and value come from the counters, read here only: no live registers)
@@ -1739,7 +1483,6 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
             r = __shfl(r, gbase);   // the group's leader holds the group's slot
             if (!active && member && r < qlen) take(r, r < qlong ? r : P.queue_cap - 1u - (r - qlong));   // long rays first
         }
-        INSITU_T_MARK(0)
         if (__ballot(active) == 0ull) {
             if (drained) break;
             continue;
@@ -1782,9 +1525,6 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
                     wback = f4{__shfl(wback.x, src), __shfl(wback.y, src), __shfl(wback.z, src), __shfl(wback.w, src)};
                     e0 = (size_t)(uint32_t)__shfl((int)(uint32_t)e0, src) |
                          ((size_t)(uint32_t)__shfl((int)(uint32_t)(e0 >> 32), src) << 32);
-#ifdef INSITU_DEBUG_REPLAYS
-                    dbg_rounds = (uint32_t)__shfl((int)dbg_rounds, src);
-#endif
                     if (lane == 0) atomicAdd(&ctr->regroups, 1u);
                     d = dn;
                     G = Gn;
@@ -1792,7 +1532,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
                     gbase = g * Gn;
                     member = g < R;
                     leader_lane = member && nd == 0;
-                    spec_from = INSITU_SPEC_FROM_GROUP;
+                    spec_from = kSpecFromGroup;
                     active = member;
                     nchunks = (n + 3) >> 2;
                     if (active) {   // the ray's next round (k = 0, as at the round end that led here)
@@ -1808,8 +1548,6 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
                 }
             }
         }
-        INSITU_T_MARK(1)
-        INSITU_DIAG_COUNT(2, active && k < n && !hold);   // [2] replaying lanes, [6] wave trips
         if (active && k < n && !hold) {
             // chunk 0 comes from LDS when a pass starts, every later chunk was loaded one trip ahead
             if (k == 0) {
@@ -1839,38 +1577,12 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
             const f4 x0 = classify_sample(c4.x, s_tf, P.xfer.n_tf, s_cm, P.xfer.n_cm);
             const f4 x1 = classify_sample(c4.y, s_tf, P.xfer.n_tf, s_cm, P.xfer.n_cm);
             const f4 x2 = classify_sample(c4.z, s_tf, P.xfer.n_tf, s_cm, P.xfer.n_cm);
-#ifdef INSITU_ABL_CLASSIFY2
-            // timing ablation: a second classification of the 4 samples folded in with weight 0.
-            // 1: the same coordinates (bank conflicts as the real lookups); 2: one coordinate for
-            // the whole wave (broadcast reads: no conflicts); 3: the VALU work only (no LDS reads)
-            f4 x3 = classify_sample(c4.w, s_tf, P.xfer.n_tf, s_cm, P.xfer.n_cm);
-            {
-                const float zz = g_abl_zero;
-#if INSITU_ABL_CLASSIFY2 == 2
-                const float u = zz + 0.3f;
-#define INSITU_ABL_C(v) classify_sample(u + (v) * zz, s_tf, P.xfer.n_tf, s_cm, P.xfer.n_cm)
-#elif INSITU_ABL_CLASSIFY2 == 3
-#define INSITU_ABL_C(v) classify_fake((v) + zz, P.xfer.n_tf, P.xfer.n_cm)
-#else
-#define INSITU_ABL_C(v) classify_sample((v) + zz, s_tf, P.xfer.n_tf, s_cm, P.xfer.n_cm)
-#endif
-                const f4 y0 = INSITU_ABL_C(c4.x);
-                const f4 y1 = INSITU_ABL_C(c4.y);
-                const f4 y2 = INSITU_ABL_C(c4.z);
-                const f4 y3 = INSITU_ABL_C(c4.w);
-#undef INSITU_ABL_C
-                x3.x = __builtin_fmaf((y0.x + y0.y) + (y0.z + y0.w) + (y1.x + y1.y) + (y1.z + y1.w) + (y2.x + y2.y) +
-                                          (y2.z + y2.w) + (y3.x + y3.y) + (y3.z + y3.w), zz, x3.x);
-            }
-#else
             const f4 x3 = classify_sample(c4.w, s_tf, P.xfer.n_tf, s_cm, P.xfer.n_cm);
-#endif
             const bool write = q.written && node == 0;
-            // INSITU_SPEC_WRITE: the root's search passes store too (into the ray's own slots, which the
+            // the root's search passes store too (into the ray's own slots, which the
             // accepted pass or the write pass overwrites; readers stop at the final count)
-            const bool store = (q.written || (INSITU_SPEC_WRITE && q.iter + 1 >= spec_from)) && node == 0;
+            const bool store = (q.written || q.iter + 1 >= spec_from) && node == 0;
             auto emit = [&](float s0, float e1, const f4& cv, int steps) {
-                INSITU_DIAG_COUNT(4, store);   // [8] storing lanes per closing block, [12] such blocks
                 if (store) {
                     // stored supersegments: raw curV + step count, adjusted colour and octree cells
                     // done afterwards (vdi_finish_kernel); the ones past S are not stored, their
@@ -1893,8 +1605,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
             };
             // a search pass that has closed more than S supersegments is decided (the walk only asks
             // n > S, n < S - delta or n == 0): the lane skips the rest of it (k = n)
-#if INSITU_SEL_REPLAY
-            if constexpr (FILTERED && INSITU_SPEC_WRITE) {
+            if constexpr (FILTERED) {
                 // the select form: no branch per sample (seg_sample_sel); a lane past its pass's end changes nothing
                 // (merged volumes: a storing lane advances the ray parameter to the sample's step first)
 #define INSITU_REPLAY_SEL(XV, WV, SI)                                                                          \
@@ -1912,7 +1623,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
         } else {                                                                                               \
             last = last_final && k == n - 1;                                                                   \
         }                                                                                                      \
-        seg_sample_sel<INSITU_SEARCH_PRE>(st, (XV), (WV), stp, on, last, th, wfront, wback, nw, P.xfer.cmag, emit, store); \
+        seg_sample_sel(st, (XV), (WV), stp, on, last, th, wfront, wback, nw, emit, store);                     \
         if constexpr (!MERGED) stp = stp + nw;                                                                 \
         k = on ? ((!q.written && st.nterm > S) ? n : k + 1) : k;                                               \
     }
@@ -1921,9 +1632,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
                 INSITU_REPLAY_SEL(x2, w4.z, s4.y & 0xffffu)
                 INSITU_REPLAY_SEL(x3, w4.w, s4.y >> 16)
 #undef INSITU_REPLAY_SEL
-            } else
-#endif
-            {
+            } else {   // exact_search: the branching form, every decision exact
 #define INSITU_REPLAY(XV, WV, SI)                                                                              \
     if (k < n) {                                                                                               \
         bool last;                                                                                             \
@@ -1938,8 +1647,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
         } else {                                                                                               \
             last = last_final && k == n - 1;                                                                \
         }                                                                                                      \
-        seg_sample<FILTERED, INSITU_SPEC_WRITE ? 1 : 2, true, INSITU_SEARCH_PRE>(st, (XV), (WV), stp, ndc_of, last, th, wfront, \
-                                      wback, nw, P.xfer.cmag, emit, store);                                    \
+        seg_sample<true, true>(st, (XV), (WV), stp, ndc_of, last, th, wfront, wback, nw, emit);                \
         if constexpr (!MERGED) stp = stp + nw;                                                                 \
         k = (!q.written && st.nterm > S) ? n : k + 1;                                                          \
     }
@@ -1950,7 +1658,6 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
 #undef INSITU_REPLAY
             }
         }
-        INSITU_T_MARK(2)
         // end of a round once every lane of the group has finished its pass
         const unsigned long long fin = __ballot(active && k >= n);
         const unsigned long long gmask = ((1ull << G) - 1ull) << gbase;   // G <= 63
@@ -1958,14 +1665,12 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
         const unsigned long long re = __ballot(round_end);
         if (re == 0ull) continue;
         // the end-of-round code runs with only the finishing lanes active: batch it
-        if (__popcll(re) < (G == 1 ? P.round_batch : INSITU_GROUP_BATCH) && __ballot(active && k < n && !hold) != 0ull) continue;
-        INSITU_T_MARK(3)
-        INSITU_DIAG_COUNT(3, round_end);         // [3] lanes ending a round, [7] wave round-end blocks
+        if (__popcll(re) < (G == 1 ? P.round_batch : kGroupBatch) && __ballot(active && k < n && !hold) != 0ull) continue;
         // publish the pass results of the group's tree nodes (lanes gbase .. gbase+G-1); the lanes
         // of one wave read each other's entries in order, no block barrier needed
         if (round_end) {
-            float lo = INSITU_SPEC_WRITE ? st.lo : st.startPt, hi = INSITU_SPEC_WRITE ? st.hi : st.endPt;
-            if constexpr (FILTERED && INSITU_SEARCH_PRE) {   // bounds from the recorded extreme estimates
+            float lo = st.lo, hi = st.hi;
+            if constexpr (FILTERED) {   // bounds from the recorded extreme estimates
                 lo = __builtin_fmaxf(lo, seg_lo_bound(st.lo_a, P.xfer.cmag));
                 hi = __builtin_fminf(hi, seg_hi_bound(st.hi_a, P.xfer.cmag));
             }
@@ -1974,7 +1679,6 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        INSITU_T_MARK(3)   // (the round-end checks and the publication of the pass results)
         if (round_end) {
             bool done = q.written;
             if (done) {
@@ -1985,7 +1689,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
                 float4 iv = s_iv[home];
                 int n_high = s_nh[home];
                 int at = 0;
-                bool stored = false;   // INSITU_SPEC_WRITE: accepted at the root's threshold, whose pass stored
+                bool stored = false;   // accepted at the root's threshold, whose pass stored
                 for (int lvl = 0; lvl < d; ++lvl) {
                     const float4 res = s_res[tid - node + at];   // lane gbase + at of this wave
                     const int cnt_here = __float_as_int(res.x);
@@ -1993,14 +1697,13 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
                     const bool more = cnt_here > S;
                     const bool narrow = __builtin_fabsf(q.high - q.low) < 0.000001f;   // found there moves mid
                     search_step(q, cnt_here, S, delta, res.y, res.z, iv, n_high);
-                    stored = INSITU_SPEC_WRITE && lvl == 0 && q.found && !narrow && q.iter >= spec_from;
+                    stored = lvl == 0 && q.found && !narrow && q.iter >= spec_from;
                     if (q.found || q.iter >= 64) break;
                     at = more ? 2 * at + 1 : 2 * at + 2;
                 }
                 if (q.iter < 64) free_walk(q, iv, n_high, S, delta);
                 s_iv[home] = iv;
                 s_nh[home] = n_high;
-                INSITU_T_MARK(6)   // (the tree walk and the free walk)
                 if (q.iter + 1 > 64) {   // :405 -- the next pass would exceed the reference's cap
                     q.iter++;
                     nseg = 0;            // (nothing written: a speculative pass's stores are not the output)
@@ -2015,9 +1718,6 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
                     k = 0;
                     nseg = 0;
                     stp = step_first;
-#ifdef INSITU_DEBUG_REPLAYS
-                    dbg_rounds++;
-#endif
                 }
             }
             if (done) {
@@ -2033,13 +1733,9 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
             e[0] = s_dbg_t0[home];
             e[1] = wall_clock64();
             e[2] = (unsigned long long)q.iter | ((unsigned long long)n << 8) | ((unsigned long long)G << 24);
-#ifdef INSITU_DEBUG_REPLAYS
-            e[2] |= (unsigned long long)dbg_rounds << 32;
-#endif
             e[3] = pix | ((unsigned long long)bslot << 32);
         }
     }
-    INSITU_T_FLUSH()
 }
 
 // rows 2 and 3 of pv in LDS after the search loop's per-lane arrays (ndc_at_rows)
@@ -2053,13 +1749,14 @@ __device__ __forceinline__ void stage_pv_rows(const VdiGenParams& P, float4* sme
 }
 
 template <bool FILTERED, bool MERGED>
-__global__ __launch_bounds__(256, INSITU_SEARCH_MIN_WAVES) void vdi_search_kernel(const VdiGenParams P) {
+__global__ __launch_bounds__(256, kSearchMinWaves) void vdi_search_kernel(const VdiGenParams P) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
     stage_luts(P.xfer, smem, reinterpret_cast<float*>(smem + lut_cm_slots(P.xfer.n_cm)));
     stage_pv_rows(P, smem);
     search_loop<FILTERED, MERGED>(P, smem);
 }
 
+constexpr int kFinishMinBlocks = 1;   // vdi_finish_kernel: waves per SIMD asked of the compiler
 // The stored supersegments the generator left pending: their octree cell counts
 // (AccumulateVDI.comp:143-177) and, for the search kernel's rays, their adjusted colours
 // (AccumulateVDI.comp:50-54, from the raw curV and step count stored in the slot).  One lane per
@@ -2070,7 +1767,7 @@ __global__ __launch_bounds__(256, INSITU_SEARCH_MIN_WAVES) void vdi_search_kerne
 // The 64 pixels of a tile normally share one grid cell (8x8 pixels per cell, DistributedVolumes.kt:342),
 // so their counts meet in a per-wave LDS histogram over the S z intervals and reach HBM as at most
 // S atomics per tile instead of one contended atomic per (supersegment, interval).
-__global__ __launch_bounds__(256, INSITU_FINISH_MIN_BLOCKS) void vdi_finish_kernel(const VdiGenParams P) {
+__global__ __launch_bounds__(256, kFinishMinBlocks) void vdi_finish_kernel(const VdiGenParams P) {
     extern __shared__ uint32_t s_hist[];   // S counters per wave
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     uint32_t* hist = s_hist + wave * P.S;
@@ -2283,36 +1980,6 @@ hipError_t launch_vdi_search(const VdiGenParams& p, hipStream_t s) {
     }
     if (f) hipLaunchKernelGGL((vdi_search_kernel<true, false>), dim3(p.search_blocks), dim3(256), lds_search, s, p);
     else hipLaunchKernelGGL((vdi_search_kernel<false, false>), dim3(p.search_blocks), dim3(256), lds_search, s, p);
-#ifdef INSITU_DIAG_TIME
-    {
-        unsigned long long h[8] = {};
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_dtime), sizeof h);
-        const unsigned long long z[8] = {};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_dtime), z, sizeof z);
-        const double tot = (double)(h[0] + h[1] + h[2] + h[3] + h[4]);
-        const double tot8 = tot + (double)(h[5] + h[6]);
-        std::fprintf(stderr, "[dtime] search wave cycles %.4g: claim %.3f take %.3f regroup %.3f replay %.3f checks+publish %.3f walk %.3f thr+done %.3f\n",
-                     tot8, h[5] / tot8, h[0] / tot8, h[1] / tot8, h[2] / tot8, h[3] / tot8, h[6] / tot8, h[4] / tot8);
-    }
-#endif
-#ifdef INSITU_DIAG
-    {
-        unsigned long long h[16] = {};
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_diag), sizeof h);
-        const unsigned long long z[16] = {};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_diag), z, sizeof z);
-        std::fprintf(stderr, "[diag] filtered decisions %llu, exact fallbacks %llu (%.3f%%); wave calls %llu, with a fallback %llu (%.2f%%)\n",
-                     h[0], h[1], 100.0 * (double)h[1] / (double)(h[0] ? h[0] : 1), h[4], h[5],
-                     100.0 * (double)h[5] / (double)(h[4] ? h[4] : 1));
-        std::fprintf(stderr, "[diag] search trips %llu, replaying lanes per trip %.2f; round-end blocks %llu (%.3f per trip), lanes per block %.2f\n",
-                     h[6], (double)h[2] / (double)(h[6] ? h[6] : 1), h[7], (double)h[7] / (double)(h[6] ? h[6] : 1),
-                     (double)h[3] / (double)(h[7] ? h[7] : 1));
-        std::fprintf(stderr, "[diag] close blocks %llu (%.3f per trip), writing lanes %llu (%.2f per block with any)\n",
-                     h[12], (double)h[12] / (double)(h[6] ? h[6] : 1), h[8], (double)h[8] / (double)(h[12] ? h[12] : 1));
-    }
-#endif
     return hipGetLastError();
 }
 

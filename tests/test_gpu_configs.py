@@ -135,7 +135,7 @@ def test_config2_full_frame_8_bricks(sim_n):
     ctx, img = _render(sc)
     st = ctx.stats()
     mp, hit = ctx.pass_stats()
-    print(f"[configs] sim{sim_n}: rays searched {st['rays_searched']}, search regroups {st.get('regroups')}, "
+    print(f"[configs] sim{sim_n}: rays searched {st['rays_searched']}, search regroups {st.get('search_regroups')}, "
           f"mean passes {mp:.3f} over {hit} hit rays", flush=True)
     comp = InSituContext(sc["W"], sc["H"], max_supersegments=S, bricks_per_rank=len(sc["vols"]), composite_vdi=True,
                          max_output_supersegments=S)

@@ -914,7 +914,7 @@ def test_super_tile_order_bit_exact(sup):
 def test_vdi_compositor_cached_search_bit_exact(exact):
     """VDICompositor with the merge cache grown to the demand (the second frame: every wave replays its
     cached sequence -- 32-byte entries, the world positions recomputed from the depths
-    (INSITU_COMP_ENTRY_WORLD 0) -- with filtered decisions and the interval walk; exact = 1: every decision by
+    -- with filtered decisions and the interval walk; exact = 1: every decision by
     the exact path) -- composited VDI and pass counts equal the oracle's, three lists."""
     W, H, S, S_out = 72, 56, 8, 6
     scs = [make_scene(n=24, W=W, H=H, yaw=120.0),

@@ -121,7 +121,7 @@ def _run(ctx, trigger, composite=False, S_out=0, nframes=5, reingest_after=2, al
 @pytest.mark.parametrize("trigger", [1, 0, 2])
 def test_pipelined_frames_bit_exact(trigger):
     """Five pipelined frames (different cameras, a re-ingest between frames 2 and 3) under each trigger of
-    the next frame's first pass: at the previous search's queue drain (1, default), after it (0), at once (2)
+    the next frame's first pass: at the previous search's queue drain (1), after it (0), at once (2, default)
     -- every frame's sub-VDIs, octree cells, pass counts and flattened image bit for bit."""
     with _ctx() as ctx:
         _run(ctx, trigger)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds a variant of libinsitu_hip.so with extra compile flags (experiments and diagnostics):
-#   tools/variant_build.sh NAME "-DINSITU_DIAG ..."  ->  scenery-insitu_amd/lib/variants/libinsitu_hip_NAME.so
+#   tools/variant_build.sh NAME "-Rpass-analysis=kernel-resource-usage ..."  ->  scenery-insitu_amd/lib/variants/libinsitu_hip_NAME.so
 # Run it with INSITU_HIP_LIB=scenery-insitu_amd/lib/variants/libinsitu_hip_NAME.so (insitu_amd/native.py).
 set -e
 cd "$(dirname "$0")/../scenery-insitu_amd"
