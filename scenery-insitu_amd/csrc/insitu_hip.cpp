@@ -102,45 +102,61 @@ struct Tuning {
     long long exact_tile_keys = 0;  // 1: tile keys from all 64 rays of a tile (0: 16 of them)
 };
 
-// hipEvent slots of a frame (insitu_ctx::ev): [0] render start, [1] render end (send buffers ready),
-// [2] exchange end, [3] composite end, [4] gather end, [5] sample / search split, [6] compaction start,
-// [7] (local group) this rank's copies out of its peers' buffers are done -- recorded after its exchange and
-// its gather; a peer's next render/composite waits on it before rewriting them, [8] exchange counts in,
-// [9] payload start, [10] the root's image copied to the host buffer of insitu_gather, [11] (pipelined) the
-// frame's completion is done: its slot may be rendered into again, [12] compaction end, [13] (pipelined)
-// search end: the next frame's sampling may start (trigger mode 0)
-constexpr int kFrameEvents = 14;
+// hipEvents of a frame (FrameSlot::ev).  EvRenderStart..EvGatherEnd stay consecutive: the stage times of
+// insitu_get_stats are the spans ev[i], ev[i + 1] over them.
+enum FrameEvent {
+    EvRenderStart = 0,
+    EvRenderEnd,       // the send buffers are ready
+    EvExchangeEnd,
+    EvCompositeEnd,
+    EvGatherEnd,
+    EvSampleEnd,       // sample / search split
+    EvCompactStart,
+    EvPeerReadsDone,   // (local group) this rank's copies out of its peers' buffers are done -- recorded after its
+                       // exchange and its gather; a peer's next render/composite waits on it before rewriting them
+    EvCountsIn,        // exchange counts in
+    EvPayloadStart,
+    EvImageOnHost,     // the root's image copied to the host buffer of insitu_gather
+    EvSlotFree,        // (pipelined) the frame's completion is done: its slot may be rendered into again
+    EvCompactEnd,
+    EvSearchEnd,       // (pipelined) the next frame's sampling may start (trigger mode 0)
+    kFrameEvents
+};
 
 // The generator's per-frame buffers and the frame's camera, events and stage flags.  Pipelined frames
-// (insitu_frame_pipelined) render frame k+1 into one set while frame k is composited from the other: the
-// insitu_ctx members listed in swap_slot hold the set of the frame the stage functions work on, `alt` holds
-// the other (swap_slot exchanges them).  Unpipelined contexts use one set (alt stays empty).
+// (insitu_frame_pipelined) render frame k+1 into one slot while frame k is composited from the other:
+// insitu_ctx::cur points at the slot of the frame the stage functions work on, insitu_ctx::alt at the other
+// (swap_slot exchanges the pointers).  Unpipelined contexts use one slot (the other stays empty).
 struct FrameSlot {
     float4* vcol_send = nullptr;
     float2* vdep_send = nullptr;
     uint32_t* octree = nullptr;
     uint8_t* passes = nullptr;
-    uint16_t* seg_pending = nullptr;
-    uint16_t* seg_steps = nullptr;
-    GenCounters* counters = nullptr;
-    PendingRay* queue = nullptr;
-    float* cache = nullptr;
+    uint16_t* seg_pending = nullptr;    // per brick and pixel: supersegments awaiting vdi_finish_kernel
+    uint16_t* seg_steps = nullptr;      // per sub-VDI entry: step count of a deferred colour
+    GenCounters* counters = nullptr;    // cache cursor + search queue counters
+    PendingRay* queue = nullptr;        // rays queued for the search kernel (B*W*H)
+    float* cache = nullptr;             // per-sample raymarch cache (32-byte chunks of 4 samples)
     uint32_t cache_chunks = 0;
-    uint32_t cache_grow_to = 0;
-    bool cache_sized = false;
-    GenCounters* h_ctr = nullptr;
-    bool h_ctr_pending = false;
-    bool h_ctr_valid = false;
-    bool search_launched = false;
-    uint32_t* tile_keys = nullptr;
+    // default-sized caches (insitu_ctx::cache_adaptive) grow to the measured demand: the frame's cursor (chunks
+    // asked for) is copied to pinned h_ctr at the end of every render, read after the next synchronisation
+    uint32_t cache_grow_to = 0;         // > cache_chunks: reallocate before the next render
+    bool cache_sized = false;           // the default cache was sized from a frame's measured demand
+    GenCounters* h_ctr = nullptr;       // pinned copy of `counters` (valid after a synchronisation)
+    bool h_ctr_pending = false;         // h_ctr's copy was enqueued and not yet observed after a synchronisation
+    bool h_ctr_valid = false;           // h_ctr holds the last render's counters (observed after a synchronisation)
+    bool search_launched = false;       // a render ran the persistent search kernel (fault flag valid)
+    uint32_t* tile_keys = nullptr;      // longest-tiles-first order: keys / ids (2 x B*tiles each)
     uint32_t* tile_ids = nullptr;
-    unsigned char* sort_tmp = nullptr;
+    unsigned char* sort_tmp = nullptr;  // hipcub temporary storage (insitu_ctx::sort_tmp_bytes)
     float ipv[16] = {}, pv[16] = {}, view[16] = {};
-    bool rendered = false, composited = false, exchanged = false;
+    bool rendered = false, composited = false;
+    bool exchanged = false;             // the compositor's input lists are complete (VDI set readable)
     bool pipelined = false;   // rendered by insitu_frame_pipelined (compaction runs with the completion)
     hipStream_t search_stream = nullptr;   // pipelined: the slot's search, finish and counter copy run here
-    int flag_index = 1;                    // pipelined: the slot's drain trigger, insitu_ctx::pipe_flag[flag_index]
-    hipEvent_t ev[kFrameEvents] = {};
+    int flag_index = 0;                    // the slot's index in insitu_ctx::slots; pipelined: its drain trigger
+                                           // is insitu_ctx::pipe_flag[flag_index]
+    hipEvent_t ev[kFrameEvents] = {};      // (FrameEvent above)
     bool ev_valid[kFrameEvents] = {};
 };
 
@@ -162,14 +178,8 @@ struct insitu_ctx {
     int n_tf = 0, n_cm = 0;
     float cmag = 1.0f;                  // TransferDesc::cmag of the current LUTs
     float conv_scale = 1.0f, conv_offset = 0.0f;
-    float4* d_vcol_send = nullptr;
-    float2* d_vdep_send = nullptr;
     float4* d_vcol_recv = nullptr;
     float2* d_vdep_recv = nullptr;
-    uint32_t* d_octree = nullptr;
-    uint8_t* d_passes = nullptr;
-    uint16_t* d_seg_pending = nullptr;  // per brick and pixel: supersegments awaiting vdi_finish_kernel
-    uint16_t* d_seg_steps = nullptr;    // per sub-VDI entry: step count of a deferred colour
     uint32_t* d_pcol_send = nullptr;
     uint32_t* d_pdep_send = nullptr;
     uint32_t* d_pcol_recv = nullptr;
@@ -190,32 +200,17 @@ struct insitu_ctx {
     uint32_t* h_tot = nullptr;          // pinned copy of d_cursor
     size_t meta_bytes = 0;
     bool camera_set = false;
-    float* d_cache = nullptr;           // per-sample raymarch cache (32-byte chunks of 4 samples)
     void* d_staging = nullptr;          // host-buffer brick uploads (kept: re-ingest every N frames)
     size_t staging_bytes = 0;
-    GenCounters* d_counters = nullptr;  // cache cursor + search queue counters
-    PendingRay* d_queue = nullptr;      // rays queued for the search kernel (B*W*H)
-    uint32_t cache_chunks = 0;
-    // default-sized caches grow to the measured demand: the frame's cursor (chunks asked for) is
-    // copied to pinned h_ctr at the end of every render, read after the next synchronisation
-    bool cache_adaptive = false;
+    bool cache_adaptive = false;        // a default-sized sample cache: the slots' caches grow (FrameSlot)
     size_t cache_max_chunks = 0;        // growth limit (45 % of the HBM free at create, 2^32 chunks)
-    uint32_t cache_grow_to = 0;         // > cache_chunks: reallocate before the next render
-    GenCounters* h_ctr = nullptr;       // pinned copy of d_counters (valid after a synchronisation)
-    bool cache_sized = false;           // the default cache was sized from a frame's measured demand
-    bool h_ctr_pending = false;         // h_ctr's copy was enqueued and not yet observed after a synchronisation
-    bool h_ctr_valid = false;           // h_ctr holds the last render's counters (observed after a synchronisation)
     int num_cus = 256;
     int search_blocks = 0;
     int search_lanes = 0;               // resident lanes of the search grid for the LUT sizes below
     int search_lanes_tf = -1, search_lanes_cm = -1;
     Tuning tune;
-    bool search_launched = false;       // a render ran the persistent search kernel (fault flag valid)
     unsigned long long* d_dbg = nullptr;   // INSITU_DEBUG_RAYS: per-round search timing
-    uint32_t* d_tile_keys = nullptr;       // longest-tiles-first order: keys / ids (2 x B*tiles each)
-    uint32_t* d_tile_ids = nullptr;
-    unsigned char* d_sort_tmp = nullptr;   // hipcub temporary storage
-    size_t sort_tmp_bytes = 0;
+    size_t sort_tmp_bytes = 0;          // of the slots' hipcub temporary storage
     size_t dbg_entries = 0;
     std::string dbg_path;
     bool dbg_pending = false;
@@ -238,19 +233,17 @@ struct insitu_ctx {
     unsigned long long cseq_demand = 0; // the demand observed after the last composite's synchronisation
     unsigned long long cseq_cap = 0;    // capacity (entries)
     unsigned long long cseq_max = 0;    // growth limit (entries): 20 % of the HBM free at create
-    float ipv[16], pv[16], view[16];
-    bool rendered = false, composited = false;
-    bool exchanged = false;             // the compositor's input lists are complete (VDI set readable)
-    bool slot_pipelined = false;        // this slot's frame was rendered by insitu_frame_pipelined
-    hipStream_t slot_search_stream = nullptr;   // pipelined: this slot's search stream (FrameSlot::search_stream)
-    int slot_flag_index = 0;            // pipelined: this slot's trigger flag (FrameSlot::flag_index)
-    hipEvent_t ev[kFrameEvents] = {};   // (kFrameEvents above)
-    bool ev_valid[kFrameEvents] = {};
-    // cross-frame pipelining (insitu_frame_pipelined, DistributedVolumeRenderer.kt:530-542: the composite is
-    // one frame stale): the other frame's buffers, the sampling and completion streams, the trigger flag
-    FrameSlot alt;
-    bool pipe_ready = false;            // alt allocated, streams created
-    bool pipe_inflight = false;         // alt holds a rendered frame whose completion is pending
+    // the frame slots: `cur` is the one the stage functions work on.  Cross-frame pipelining
+    // (insitu_frame_pipelined, DistributedVolumeRenderer.kt:530-542: the composite is one frame stale) fills
+    // the second one, `alt`, and adds the sampling and completion streams and the trigger flags below
+    FrameSlot slots[2];
+    FrameSlot* cur = &slots[0];
+    FrameSlot* alt = &slots[1];
+    insitu_ctx() { slots[1].flag_index = 1; }
+    insitu_ctx(const insitu_ctx&) = delete;   // (cur and alt point into the context)
+    insitu_ctx& operator=(const insitu_ctx&) = delete;
+    bool pipe_ready = false;            // *alt allocated, streams created
+    bool pipe_inflight = false;         // *alt holds a rendered frame whose completion is pending
     bool completing = false;            // insitu_frame_pipelined is running the stages of the frame one behind
     bool ingest_batch = false;          // re-ingests since the last render: ev_ingest0 marks their start
     hipEvent_t ev_ingest0 = nullptr, ev_ingest = nullptr;   // the last batch of re-ingests (start, end)
@@ -305,44 +298,44 @@ int dev_alloc(insitu_ctx* c, T** p, size_t count) {
     return 0;
 }
 
+// frees what alloc_slot and pipeline_setup gave a slot (any of it may be missing: a failed create); the streams
+// that use the slot are idle
+void free_slot(FrameSlot& f) {
+    void* ptrs[] = {f.vcol_send, f.vdep_send, f.octree, f.passes, f.seg_pending, f.seg_steps, f.counters, f.queue,
+                    f.cache, f.tile_keys, f.tile_ids, f.sort_tmp};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    if (f.h_ctr) (void)hipHostFree(f.h_ctr);
+    for (auto& e : f.ev)
+        if (e) (void)hipEventDestroy(e);
+    if (f.search_stream) (void)hipStreamDestroy(f.search_stream);
+}
+
 void release(insitu_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     // every stream first: a pipelined frame left in flight (no insitu_pipeline_flush) still runs on the sampling,
     // search and completion streams and reads the buffers, events and trigger flags freed below (each of its
     // waits has its producer enqueued ahead of it, so these synchronisations end)
-    for (hipStream_t st : {c->stream, c->pipe_sample, c->slot_search_stream, c->alt.search_stream, c->pipe_comp})
+    for (hipStream_t st : {c->stream, c->pipe_sample, c->pipe_comp})
         if (st) (void)hipStreamSynchronize(st);
+    for (FrameSlot& f : c->slots)
+        if (f.search_stream) (void)hipStreamSynchronize(f.search_stream);
     for (auto& b : c->bricks)
         if (b.d) (void)hipFree(b.d);
-    void* ptrs[] = {c->d_tf, c->d_cmap, c->d_vcol_send, c->d_vdep_send, c->d_vcol_recv, c->d_vdep_recv,
-                    c->d_octree, c->d_passes, c->d_seg_pending, c->d_seg_steps, c->d_pcol_send, c->d_pdep_send, c->d_pcol_recv, c->d_pdep_recv,
-                    c->d_strip, c->d_gather, c->d_image, c->d_cache, c->d_counters, c->d_queue, c->d_cvdi_col, c->d_cvdi_dep, c->d_gvdi_col, c->d_gvdi_dep, c->d_cvdi_cnt, c->d_gvdi_cnt, c->d_cpasses, c->d_cseq, c->d_cseq_cursor, c->d_ref_col, c->d_ref_dep,
-                    c->d_dbg, c->d_tile_keys, c->d_tile_ids, c->d_sort_tmp, c->d_ref_cnt, c->d_ccol_send, c->d_cdep_send, c->d_meta_send, c->d_meta_recv, c->d_cursor, c->d_staging};
+    void* ptrs[] = {c->d_tf, c->d_cmap, c->d_vcol_recv, c->d_vdep_recv, c->d_pcol_send, c->d_pdep_send, c->d_pcol_recv, c->d_pdep_recv,
+                    c->d_strip, c->d_gather, c->d_image, c->d_cvdi_col, c->d_cvdi_dep, c->d_gvdi_col, c->d_gvdi_dep, c->d_cvdi_cnt, c->d_gvdi_cnt, c->d_cpasses, c->d_cseq, c->d_cseq_cursor, c->d_ref_col, c->d_ref_dep,
+                    c->d_dbg, c->d_ref_cnt, c->d_ccol_send, c->d_cdep_send, c->d_meta_send, c->d_meta_recv, c->d_cursor, c->d_staging};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    for (auto& e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    {   // the other frame slot (pipelined contexts)
-        FrameSlot& a = c->alt;
-        void* aptrs[] = {a.vcol_send, a.vdep_send, a.octree, a.passes, a.seg_pending, a.seg_steps, a.counters, a.queue,
-                         a.cache, a.tile_keys, a.tile_ids, a.sort_tmp};
-        for (void* p : aptrs)
-            if (p) (void)hipFree(p);
-        for (auto& e : a.ev)
-            if (e) (void)hipEventDestroy(e);
-        if (a.h_ctr) (void)hipHostFree(a.h_ctr);
-    }
+    for (FrameSlot& f : c->slots) free_slot(f);
     if (c->ev_ingest) (void)hipEventDestroy(c->ev_ingest);
     if (c->ev_ingest0) (void)hipEventDestroy(c->ev_ingest0);
     if (c->ev_gate) (void)hipEventDestroy(c->ev_gate);
     if (c->pipe_flag) (void)hipFree(c->pipe_flag);
-    for (hipStream_t st : {c->slot_search_stream, c->alt.search_stream})
-        if (st) (void)hipStreamDestroy(st);
     if (c->pipe_sample) (void)hipStreamDestroy(c->pipe_sample);
     if (c->pipe_comp) (void)hipStreamDestroy(c->pipe_comp);
     if (c->h_tot) (void)hipHostFree(c->h_tot);
-    if (c->h_ctr) (void)hipHostFree(c->h_ctr);
     if (c->h_cseq_demand) (void)hipHostFree(c->h_cseq_demand);
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->group && c->rank < (int)c->group->ranks.size() && c->group->ranks[c->rank] == c) c->group->ranks[c->rank] = nullptr;
@@ -351,40 +344,8 @@ void release(insitu_ctx* c) {
 
 bool is_root(const insitu_ctx* c) { return c->rank == 0; }
 
-// exchange the current frame slot's members with `alt` (FrameSlot)
-void swap_slot(insitu_ctx* c) {
-    FrameSlot& a = c->alt;
-    std::swap(c->d_vcol_send, a.vcol_send);
-    std::swap(c->d_vdep_send, a.vdep_send);
-    std::swap(c->d_octree, a.octree);
-    std::swap(c->d_passes, a.passes);
-    std::swap(c->d_seg_pending, a.seg_pending);
-    std::swap(c->d_seg_steps, a.seg_steps);
-    std::swap(c->d_counters, a.counters);
-    std::swap(c->d_queue, a.queue);
-    std::swap(c->d_cache, a.cache);
-    std::swap(c->cache_chunks, a.cache_chunks);
-    std::swap(c->cache_grow_to, a.cache_grow_to);
-    std::swap(c->cache_sized, a.cache_sized);
-    std::swap(c->h_ctr, a.h_ctr);
-    std::swap(c->h_ctr_pending, a.h_ctr_pending);
-    std::swap(c->h_ctr_valid, a.h_ctr_valid);
-    std::swap(c->search_launched, a.search_launched);
-    std::swap(c->d_tile_keys, a.tile_keys);
-    std::swap(c->d_tile_ids, a.tile_ids);
-    std::swap(c->d_sort_tmp, a.sort_tmp);
-    std::swap(c->ipv, a.ipv);
-    std::swap(c->pv, a.pv);
-    std::swap(c->view, a.view);
-    std::swap(c->rendered, a.rendered);
-    std::swap(c->composited, a.composited);
-    std::swap(c->exchanged, a.exchanged);
-    std::swap(c->slot_pipelined, a.pipelined);
-    std::swap(c->slot_search_stream, a.search_stream);
-    std::swap(c->slot_flag_index, a.flag_index);
-    std::swap(c->ev, a.ev);
-    std::swap(c->ev_valid, a.ev_valid);
-}
+// the other frame slot becomes the current one
+void swap_slot(insitu_ctx* c) { std::swap(c->cur, c->alt); }
 
 // the stream the current slot's readbacks run on: a pipelined frame in flight keeps `stream` busy with the
 // next frame's search, the completion stream holds nothing of it
@@ -405,40 +366,44 @@ void cache_observe(insitu_ctx* c) {
         c->cseq_pending = false;
         c->cseq_demand = *c->h_cseq_demand;
     }
-    if (!c->h_ctr_pending) return;
-    c->h_ctr_pending = false;
-    c->h_ctr_valid = true;
-    if (!c->cache_adaptive || c->h_ctr->march_rays == 0) return;
-    const unsigned long long want = c->h_ctr->cache_cursor + c->h_ctr->cache_cursor / 4;
+    FrameSlot& f = *c->cur;
+    if (!f.h_ctr_pending) return;
+    f.h_ctr_pending = false;
+    f.h_ctr_valid = true;
+    if (!c->cache_adaptive || f.h_ctr->march_rays == 0) return;
+    const unsigned long long want = f.h_ctr->cache_cursor + f.h_ctr->cache_cursor / 4;
     const size_t to = std::min((size_t)want, c->cache_max_chunks);
-    if (to > c->cache_chunks) c->cache_grow_to = (uint32_t)to;
+    if (to > f.cache_chunks) f.cache_grow_to = (uint32_t)to;
 }
 
-// (re)allocate the sample cache to `chunks` 32-byte units; on failure nothing is left allocated and the
-// error is returned
+// (re)allocate the current slot's sample cache to `chunks` 32-byte units; on failure nothing is left allocated
+// and the error is returned
 hipError_t cache_realloc(insitu_ctx* c, size_t chunks) {
-    if (c->d_cache) (void)hipFree(c->d_cache);
-    c->d_cache = nullptr;
-    c->cache_chunks = 0;
-    hipError_t e = hipMalloc(&c->d_cache, chunks * 32);
+    FrameSlot& f = *c->cur;
+    if (f.cache) (void)hipFree(f.cache);
+    f.cache = nullptr;
+    f.cache_chunks = 0;
+    hipError_t e = hipMalloc(&f.cache, chunks * 32);
     if (e != hipSuccess) {
-        if (c->d_cache) (void)hipFree(c->d_cache);
-        c->d_cache = nullptr;
+        if (f.cache) (void)hipFree(f.cache);
+        f.cache = nullptr;
         (void)hipGetLastError();
         return e;
     }
-    c->cache_chunks = (uint32_t)chunks;
+    f.cache_chunks = (uint32_t)chunks;
     return hipSuccess;
 }
 
-// after a stream synchronisation: did a persistent kernel of the last render hit its wall-clock bound?
+// after a stream synchronisation: did a persistent kernel of the current slot's last render hit its wall-clock
+// bound?
 int check_fault(insitu_ctx* c) {
     cache_observe(c);   // (a pending copy of the frame's counters reached h_ctr: we are after a synchronisation)
-    if (!c->d_counters || !c->search_launched) return 0;
-    uint32_t f = 0;
-    if (c->h_ctr_valid) f = c->h_ctr->fault;
-    else if (hipMemcpy(&f, &c->d_counters->fault, sizeof f, hipMemcpyDeviceToHost) != hipSuccess) f = 1;
-    if (f) return fail(c, -6, "VDI search kernel exceeded its loop bound (internal error)");
+    const FrameSlot& f = *c->cur;
+    if (!f.counters || !f.search_launched) return 0;
+    uint32_t fault = 0;
+    if (f.h_ctr_valid) fault = f.h_ctr->fault;
+    else if (hipMemcpy(&fault, &f.counters->fault, sizeof fault, hipMemcpyDeviceToHost) != hipSuccess) fault = 1;
+    if (fault) return fail(c, -6, "VDI search kernel exceeded its loop bound (internal error)");
     return 0;
 }
 
@@ -447,21 +412,22 @@ float4* cvdi_col(const insitu_ctx* c) { return c->rank == 0 ? c->d_gvdi_col : c-
 float2* cvdi_dep(const insitu_ctx* c) { return c->rank == 0 ? c->d_gvdi_dep : c->d_cvdi_dep; }
 uint16_t* cvdi_cnt(const insitu_ctx* c) { return c->rank == 0 ? c->d_gvdi_cnt : c->d_cvdi_cnt; }
 
-void record_on(insitu_ctx* c, int i, hipStream_t s) {
-    if (hipEventRecord(c->ev[i], s) == hipSuccess) c->ev_valid[i] = true;
+// records the current slot's event `i`
+void record_on(insitu_ctx* c, FrameEvent i, hipStream_t s) {
+    if (hipEventRecord(c->cur->ev[i], s) == hipSuccess) c->cur->ev_valid[i] = true;
 }
-void record(insitu_ctx* c, int i) { record_on(c, i, c->stream); }
+void record(insitu_ctx* c, FrameEvent i) { record_on(c, i, c->stream); }
 
 // N > 1, VDI mode: pack the stored supersegments of the current slot's blocks bound for the other ranks into
-// the compact messages (vdi_compact_kernel), on `stream`, between events [6] and [12]
+// the compact messages (vdi_compact_kernel), on `stream`, between EvCompactStart and EvCompactEnd
 hipError_t compact_enqueue(insitu_ctx* c) {
-    record(c, 6);
+    record(c, EvCompactStart);
     hipError_t e = hipMemsetAsync(c->d_cursor, 0, sizeof(uint32_t) * (size_t)c->N, c->stream);
     if (e != hipSuccess) return e;
     CompactParams cp{};
-    cp.col = c->d_vcol_send;
-    cp.dep = c->d_vdep_send;
-    cp.pend = c->d_seg_pending;
+    cp.col = c->cur->vcol_send;
+    cp.dep = c->cur->vdep_send;
+    cp.pend = c->cur->seg_pending;
     cp.pend_stride = (size_t)c->W * (size_t)c->H;
     cp.W = c->W; cp.H = c->H; cp.S = c->S; cp.B = c->BV; cp.nstrips = c->N; cp.strip_w = c->strip_w;
     cp.strip_tiles = c->strip_tiles; cp.ytiles = (c->H + 7) / 8; cp.skip_d = c->rank;
@@ -472,7 +438,7 @@ hipError_t compact_enqueue(insitu_ctx* c) {
     cp.meta_bytes = c->meta_bytes;
     cp.cursor = c->d_cursor;
     e = launch_vdi_compact(cp, c->stream);
-    if (e == hipSuccess) record(c, 12);
+    if (e == hipSuccess) record(c, EvCompactEnd);
     return e;
 }
 
@@ -481,11 +447,18 @@ hipError_t compact_enqueue(insitu_ctx* c) {
 hipError_t wait_peer_reads(insitu_ctx* c) {
     if (!c->group) return hipSuccess;
     for (const insitu_ctx* q : c->group->ranks) {
-        if (!q || q == c || !q->ev_valid[7]) continue;
-        hipError_t e = hipStreamWaitEvent(c->stream, q->ev[7], 0);
+        if (!q || q == c || !q->cur->ev_valid[EvPeerReadsDone]) continue;
+        hipError_t e = hipStreamWaitEvent(c->stream, q->cur->ev[EvPeerReadsDone], 0);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+// a frame slot's events (all a plain-mode slot needs)
+int create_slot_events(insitu_ctx* c, FrameSlot& f) {
+    for (auto& ev : f.ev)
+        if (!ev && hipEventCreate(&ev) != hipSuccess) return fail(c, -3, "hipEventCreate failed");
+    return 0;
 }
 
 // allocate one frame slot's generator buffers (VDI mode): send blocks, octree counters, pass counts, pending
@@ -493,8 +466,7 @@ hipError_t wait_peer_reads(insitu_ctx* c) {
 // cache, the search queue, the pinned counter copy and the tile-order keys; plus the slot's events
 int alloc_slot(insitu_ctx* c, FrameSlot& f, size_t chunks) {
     int rc = 0;
-    for (auto& ev : f.ev)
-        if (!ev && hipEventCreate(&ev) != hipSuccess) return fail(c, -3, "hipEventCreate failed");
+    if ((rc = create_slot_events(c, f))) return rc;
     const size_t sendE = (size_t)c->N * (size_t)c->BV * c->blockE;
     const size_t px = (size_t)c->BV * (size_t)c->W * (size_t)c->H;
     if ((rc = dev_alloc(c, &f.vcol_send, sendE)) || (rc = dev_alloc(c, &f.vdep_send, sendE))) return rc;
@@ -626,8 +598,6 @@ int insitu_create(const insitu_config* cfg, insitu_ctx** out) {
         }
         c->own_stream = true;
     }
-    for (auto& ev : c->ev)
-        if (hipEventCreate(&ev) != hipSuccess) { c->err = "hipEventCreate failed"; return bail(-3); }
     if (hipEventCreate(&c->ev_ingest0) != hipSuccess || hipEventCreate(&c->ev_ingest) != hipSuccess ||
         hipEventCreate(&c->ev_gate) != hipSuccess) {
         c->err = "hipEventCreate failed";
@@ -688,14 +658,11 @@ int insitu_create(const insitu_config* cfg, insitu_ctx** out) {
             }
             if (chunks > 0) c->search_blocks = c->num_cus * 8;   // 32 waves per CU; waves that find the queue drained exit
         }
-        // the frame slot's buffers, allocated into `alt` and swapped in (a pipelined context allocates the
-        // second slot at its first pipelined frame)
-        rc = alloc_slot(c, c->alt, chunks);
-        swap_slot(c);
-        if (rc) return bail(rc);
-        if (chunks > 0 && start_knob) c->cache_sized = true;
+        // the first frame slot (a pipelined context allocates the second one at its first pipelined frame)
+        if ((rc = alloc_slot(c, c->slots[0], chunks))) return bail(rc);
+        if (chunks > 0 && start_knob) c->slots[0].cache_sized = true;
         if (const char* dbg = std::getenv("INSITU_DEBUG_RAYS")) {   // diagnostics (tools/ray_timing.py)
-            if (c->d_queue) {
+            if (c->slots[0].queue) {
                 c->dbg_entries = (size_t)c->BV * (size_t)c->W * (size_t)c->H;
                 if ((rc = dev_alloc(c, &c->d_dbg, c->dbg_entries * 4))) return bail(rc);
                 c->dbg_path = dbg;
@@ -739,6 +706,7 @@ int insitu_create(const insitu_config* cfg, insitu_ctx** out) {
             }
         }
     } else {
+        if ((rc = create_slot_events(c, c->slots[0]))) return bail(rc);
         c->rows = c->H / c->N;
         c->plainBlock = (size_t)c->rows * (size_t)c->W;
         c->stripPx = c->plainBlock;
@@ -883,7 +851,7 @@ int insitu_set_brick(insitu_ctx* c, int slot, const void* data, int dtype, const
     b.valid = false;
     // a pipelined frame in flight may still sample this brick (its first pass, and its search re-samples rays
     // without cache space): the ingest waits for that frame's search
-    if (c->pipe_inflight && c->alt.ev_valid[13]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->alt.ev[13], 0));
+    if (c->pipe_inflight && c->alt->ev_valid[EvSearchEnd]) HIPCHK(c, hipStreamWaitEvent(c->stream, c->alt->ev[EvSearchEnd], 0));
     if (!c->ingest_batch) {   // the first re-ingest since the last render: the batch's GPU time starts here
         HIPCHK(c, hipEventRecord(c->ev_ingest0, c->stream));
         c->ingest_batch = true;
@@ -989,9 +957,9 @@ int insitu_set_camera(insitu_ctx* c, const insitu_camera* cam) {
     } else if (!mat4_inverse(cam->view, iv) || !mat4_inverse(cam->proj, ip)) {
         return fail(c, -1, "insitu_set_camera: view or projection matrix is singular");
     }
-    mat4_mul_f(iv, ip, c->ipv);                // VDIGenerator.comp:289 (ipvG of accumulateSupseg)
-    mat4_mul_f(cam->proj, cam->view, c->pv);   // VDIGenerator.comp:290
-    std::memcpy(c->view, cam->view, sizeof c->view);
+    mat4_mul_f(iv, ip, c->cur->ipv);                // VDIGenerator.comp:289 (ipvG of accumulateSupseg)
+    mat4_mul_f(cam->proj, cam->view, c->cur->pv);   // VDIGenerator.comp:290
+    std::memcpy(c->cur->view, cam->view, sizeof c->cur->view);
     c->camera_set = true;
     return 0;
 }
@@ -1011,6 +979,7 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     int rc = insitu_set_camera(c, cam);
     if (rc) return rc;
+    FrameSlot& f = *c->cur;
     TransferDesc xf{c->d_tf, c->n_tf, c->d_cmap, c->n_cm, c->cmag};
     HIPCHK(c, wait_peer_reads(c));
     c->ingest_batch = false;
@@ -1018,15 +987,15 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
     // enqueued there), the search and the rest on `stream`
     hipStream_t ss = c->s_sample ? c->s_sample : c->stream;
     const bool pipelined = c->s_sample != nullptr;
-    hipStream_t sr = pipelined ? c->slot_search_stream : c->stream;   // the search and what follows it
-    c->slot_pipelined = pipelined;
-    if (!pipelined) record_on(c, 0, ss);   // (pipelined: at the trigger, below)
+    hipStream_t sr = pipelined ? f.search_stream : c->stream;   // the search and what follows it
+    f.pipelined = pipelined;
+    if (!pipelined) record_on(c, EvRenderStart, ss);   // (pipelined: at the trigger, below)
     if (c->mode == INSITU_MODE_VDI) {
         const size_t oct = (size_t)c->BV * (size_t)c->S * (size_t)c->ncx * (size_t)c->ncy;
-        if (oct) HIPCHK(c, hipMemsetAsync(c->d_octree, 0, oct * sizeof(uint32_t), ss));   // GridCellsToZero.comp
-        if (c->cache_grow_to > c->cache_chunks) {   // the last frame of this slot's rays did not all fit
-            const size_t grow = c->cache_grow_to, old = c->cache_chunks;
-            c->cache_grow_to = 0;   // (cleared first: a failure below is not retried every frame)
+        if (oct) HIPCHK(c, hipMemsetAsync(f.octree, 0, oct * sizeof(uint32_t), ss));   // GridCellsToZero.comp
+        if (f.cache_grow_to > f.cache_chunks) {   // the last frame of this slot's rays did not all fit
+            const size_t grow = f.cache_grow_to, old = f.cache_chunks;
+            f.cache_grow_to = 0;   // (cleared first: a failure below is not retried every frame)
             HIPCHK(c, hipStreamSynchronize(c->stream));
             HIPCHK(c, hipStreamSynchronize(ss));
             HIPCHK(c, hipStreamSynchronize(sr));
@@ -1035,37 +1004,37 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
                 // that worked, and at most that from now on
                 const size_t keep = std::max(old, grow / 2);
                 if (cache_realloc(c, keep) != hipSuccess) HIPCHK(c, cache_realloc(c, old));
-                c->cache_max_chunks = c->cache_chunks;
+                c->cache_max_chunks = f.cache_chunks;
             }
         }
         VdiGenParams p{};
         for (int b = 0; b < c->B; ++b) p.bricks[b] = brick_desc(c, c->bricks[b]);
         p.xfer = xf;
-        std::memcpy(p.ipv, c->ipv, sizeof p.ipv);
-        std::memcpy(p.pv, c->pv, sizeof p.pv);
-        std::memcpy(p.view, c->view, sizeof p.view);
+        std::memcpy(p.ipv, f.ipv, sizeof p.ipv);
+        std::memcpy(p.pv, f.pv, sizeof p.pv);
+        std::memcpy(p.view, f.view, sizeof p.view);
         p.nw = cam->nw;
         p.tmax = cam->tmax;
         p.W = c->W; p.H = c->H; p.S = c->S;
         p.strip_w = c->strip_w; p.strip_tiles = c->strip_tiles; p.nstrips = c->N; p.B = c->BV;
         p.nvolumes = c->BV != c->B ? c->B : 0;
         p.ytiles = (c->H + 7) / 8;
-        p.color = c->d_vcol_send;
-        p.depth = c->d_vdep_send;
-        p.octree = c->d_octree;
+        p.color = f.vcol_send;
+        p.depth = f.vdep_send;
+        p.octree = f.octree;
         p.octree_stride = (size_t)c->S * (size_t)c->ncx * (size_t)c->ncy;
-        p.passes = c->d_passes;
+        p.passes = f.passes;
         p.passes_stride = (size_t)c->W * (size_t)c->H;
-        p.seg_pending = c->d_seg_pending;
-        p.seg_steps = c->d_seg_steps;
+        p.seg_pending = f.seg_pending;
+        p.seg_steps = f.seg_steps;
         p.ncx = c->ncx; p.ncy = c->ncy;
         p.interval_size = (20.0f - 0.1f) / (float)c->S;   // VDIGenerator.comp:241-247
-        p.cache = c->d_cache;
-        p.split_event = c->ev[5];
-        c->ev_valid[5] = true;
-        p.cache_chunks = c->cache_chunks;
-        p.ctr = c->d_counters;
-        p.queue = c->d_queue;
+        p.cache = f.cache;
+        p.split_event = f.ev[EvSampleEnd];
+        f.ev_valid[EvSampleEnd] = true;
+        p.cache_chunks = f.cache_chunks;
+        p.ctr = f.counters;
+        p.queue = f.queue;
         p.queue_cap = (uint32_t)((size_t)c->BV * (size_t)c->W * (size_t)c->H);
         // longest-first, coarsely: rays with many samples (most work per pass, and the ones with
         // 20+ passes) are searched before the rest, so the frame does not end waiting for a long
@@ -1084,40 +1053,40 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
         p.search_depth = (int)c->tune.search_depth;
         p.regroup = (int)c->tune.regroup;
         p.exact_search = (int)c->tune.exact_search;
-        if (c->d_cache && (c->search_lanes_tf != c->n_tf || c->search_lanes_cm != c->n_cm)) {
+        if (f.cache && (c->search_lanes_tf != c->n_tf || c->search_lanes_cm != c->n_cm)) {
             // lanes the search grid keeps resident on this device with these LUT sizes (LDS)
             HIPCHK(c, vdi_search_resident_lanes(c->n_tf, c->n_cm, c->cfg.device, &c->search_lanes));
             c->search_lanes_tf = c->n_tf;
             c->search_lanes_cm = c->n_cm;
         }
         p.search_lanes = std::min(c->search_lanes, p.search_blocks * 256);
-        if (c->tune.tile_order && c->d_tile_keys) {
-            p.tile_keys = c->d_tile_keys;
+        if (c->tune.tile_order && f.tile_keys) {
+            p.tile_keys = f.tile_keys;
             p.super_tile = (int)c->tune.super_tile;
             p.tile_len_exact = (int)c->tune.exact_tile_keys;
-            p.tile_ids = c->d_tile_ids;
-            p.sort_tmp = c->d_sort_tmp;
+            p.tile_ids = f.tile_ids;
+            p.sort_tmp = f.sort_tmp;
             p.sort_tmp_bytes = c->sort_tmp_bytes;
         }
-        if (pipelined && c->d_cache && c->pipe_flag && c->pipe_trigger == 1) {
-            p.pipe_flag = c->pipe_flag + c->slot_flag_index;   // this search's queue drain starts the next first pass
+        if (pipelined && f.cache && c->pipe_flag && c->pipe_trigger == 1) {
+            p.pipe_flag = c->pipe_flag + f.flag_index;   // this search's queue drain starts the next first pass
             p.pipe_seq = c->pipe_seq;
         }
         // counters zeroed, tile keys (and, on a default cache's first frame, the frame's cache demand) sorted
-        p.measure_cache = (c->cache_adaptive && !c->cache_sized && p.nvolumes == 0) ? 1 : 0;
+        p.measure_cache = (c->cache_adaptive && !f.cache_sized && p.nvolumes == 0) ? 1 : 0;
         HIPCHK(c, launch_vdi_prepare(p, ss));
         p.prepared = 1;
-        if (p.measure_cache && c->d_cache && p.tile_ids) {
+        if (p.measure_cache && f.cache && p.tile_ids) {
             // the first frame of a default-sized cache: wait for the demand the tile keys measured and
             // size the cache to it (later frames grow it from their own demand, cache_observe)
             unsigned long long need = 0;
-            HIPCHK(c, hipMemcpyAsync(&need, &c->d_counters->cache_need, sizeof need, hipMemcpyDeviceToHost, ss));
+            HIPCHK(c, hipMemcpyAsync(&need, &f.counters->cache_need, sizeof need, hipMemcpyDeviceToHost, ss));
             HIPCHK(c, hipStreamSynchronize(ss));
-            c->cache_sized = true;
+            f.cache_sized = true;
             const size_t want = std::min((size_t)(need + need / 4 + 64), c->cache_max_chunks);
-            if (want > c->cache_chunks) HIPCHK(c, cache_realloc(c, want));
-            p.cache = c->d_cache;
-            p.cache_chunks = c->cache_chunks;
+            if (want > f.cache_chunks) HIPCHK(c, cache_realloc(c, want));
+            p.cache = f.cache;
+            p.cache_chunks = f.cache_chunks;
         }
         if (pipelined) {
             // the trigger (insitu_frame_pipelined): the prepare above only touches this slot's buffers, so its
@@ -1127,7 +1096,7 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
                 HIPCHK(c, hipStreamWaitValue64(ss, c->trig_flag, c->trig_value, hipStreamWaitValueGte));
             else if (c->trig_event)
                 HIPCHK(c, hipStreamWaitEvent(ss, c->trig_event, 0));
-            record_on(c, 0, ss);
+            record_on(c, EvRenderStart, ss);
         }
         if (c->d_dbg && !pipelined) {
             HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, c->dbg_entries * 32, ss));
@@ -1136,20 +1105,20 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
             c->dbg_pending = true;   // written to INSITU_DEBUG_RAYS at the next insitu_synchronize
         }
         HIPCHK(c, launch_vdi_sample(p, ss));
-        if (ss != sr) HIPCHK(c, hipStreamWaitEvent(sr, c->ev[5], 0));
+        if (ss != sr) HIPCHK(c, hipStreamWaitEvent(sr, f.ev[EvSampleEnd], 0));
         HIPCHK(c, launch_vdi_search(p, sr));
-        c->search_launched = c->d_cache != nullptr;
+        f.search_launched = f.cache != nullptr;
         if (pipelined) {
             // the next frame's trigger: the search is over (mode 0), or -- the flag's safety net when no wave
             // crossed the trigger point (an empty queue) -- its value is reached (mode 1)
-            record_on(c, 13, sr);
+            record_on(c, EvSearchEnd, sr);
             if (p.pipe_flag) HIPCHK(c, hipStreamWriteValue64(sr, p.pipe_flag, c->pipe_seq, 0));
         }
         HIPCHK(c, launch_vdi_finish(p, sr));
-        if (c->h_ctr) {   // the frame's counters, read on the host after the next synchronisation
-            HIPCHK(c, hipMemcpyAsync(c->h_ctr, c->d_counters, sizeof(GenCounters), hipMemcpyDeviceToHost, sr));
-            c->h_ctr_pending = true;
-            c->h_ctr_valid = false;
+        if (f.h_ctr) {   // the frame's counters, read on the host after the next synchronisation
+            HIPCHK(c, hipMemcpyAsync(f.h_ctr, f.counters, sizeof(GenCounters), hipMemcpyDeviceToHost, sr));
+            f.h_ctr_pending = true;
+            f.h_ctr_valid = false;
         }
         // variable-length exchange: the stored supersegments of the blocks bound for the other
         // ranks are packed as part of producing the send buffers (timed as the exchange); a pipelined frame
@@ -1160,7 +1129,7 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
         PlainGenParams p{};
         for (int b = 0; b < c->B; ++b) p.bricks[b] = brick_desc(c, c->bricks[b]);
         p.xfer = xf;
-        std::memcpy(p.ipv, c->ipv, sizeof p.ipv);
+        std::memcpy(p.ipv, f.ipv, sizeof p.ipv);
         p.nw = cam->nw; p.fwnw = cam->fwnw; p.tmax = cam->tmax;
         p.dim0 = c->W; p.dim1 = c->H; p.rows = c->rows;
         p.nstrips = c->N; p.B = c->B;
@@ -1168,10 +1137,10 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
         p.depth = c->d_pdep_send;
         HIPCHK(c, launch_plain_generate(p, c->stream));
     }
-    record_on(c, 1, sr);
-    c->rendered = true;
-    c->composited = false;
-    c->exchanged = false;
+    record_on(c, EvRenderEnd, sr);
+    f.rendered = true;
+    f.composited = false;
+    f.exchanged = false;
     return 0;
 }
 
@@ -1179,7 +1148,7 @@ int insitu_exchange(insitu_ctx* c) {
     if (!c) return fail(nullptr, -1, "insitu_exchange: null context");
     if (c->pipe_inflight && !c->completing)
         return fail(c, -1, "insitu_exchange: a pipelined frame is in flight (insitu_pipeline_flush first)");
-    if (!c->rendered) return fail(c, -1, "insitu_exchange: nothing rendered");
+    if (!c->cur->rendered) return fail(c, -1, "insitu_exchange: nothing rendered");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     c->last_exchange_entries = 0;
     c->last_exchange_bytes = 0;
@@ -1190,19 +1159,19 @@ int insitu_exchange(insitu_ctx* c) {
         const size_t region = (size_t)c->BV * c->blockE;
         uint32_t* send_tot = c->h_tot;
         uint32_t* recv_tot = c->h_tot + c->N;
-        if (c->group) {   // in-process: the peers packed their blocks in their renders (event [1])
+        if (c->group) {   // in-process: the peers packed their blocks in their renders (EvRenderEnd)
             for (int p = 0; p < c->N; ++p) {
                 if (p == c->rank) continue;
                 const insitu_ctx* q = c->group->ranks[p];
                 if (!q) return fail(c, -1, "insitu_exchange: local group rank " + std::to_string(p) + " missing");
-                if (!q->rendered || !q->ev_valid[1]) return fail(c, -1, "insitu_exchange: local group rank " + std::to_string(p) + " has not rendered");
-                HIPCHK(c, hipStreamWaitEvent(c->stream, q->ev[1], 0));
+                if (!q->cur->rendered || !q->cur->ev_valid[EvRenderEnd]) return fail(c, -1, "insitu_exchange: local group rank " + std::to_string(p) + " has not rendered");
+                HIPCHK(c, hipStreamWaitEvent(c->stream, q->cur->ev[EvRenderEnd], 0));
                 HIPCHK(c, hipMemcpyAsync(recv_tot + p, q->d_cursor + c->rank, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             }
             HIPCHK(c, hipMemcpyAsync(send_tot, c->d_cursor, sizeof(uint32_t) * (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
-            record(c, 8);
+            record(c, EvCountsIn);
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            record(c, 9);
+            record(c, EvPayloadStart);
             for (int p = 0; p < c->N; ++p) {
                 if (p == c->rank) continue;
                 const insitu_ctx* q = c->group->ranks[p];
@@ -1225,11 +1194,11 @@ int insitu_exchange(insitu_ctx* c) {
             NCCLCHK(c, ncclGroupEnd());
             HIPCHK(c, hipMemcpyAsync(c->h_tot, c->d_cursor, 2 * sizeof(uint32_t) * (size_t)c->N, hipMemcpyDeviceToHost,
                                      c->stream));
-            // the host learns the receive sizes: the stream idles from here ([8]) until the payload
-            // group is enqueued ([9]) -- reported as insitu_stats.ms_exchange_sync
-            record(c, 8);
+            // the host learns the receive sizes: the stream idles from here (EvCountsIn) until the payload
+            // group is enqueued (EvPayloadStart) -- reported as insitu_stats.ms_exchange_sync
+            record(c, EvCountsIn);
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            record(c, 9);
+            record(c, EvPayloadStart);
             NCCLCHK(c, ncclGroupStart());
             for (int p = 0; p < c->N; ++p) {
                 if (p == c->rank) continue;
@@ -1256,9 +1225,9 @@ int insitu_exchange(insitu_ctx* c) {
             if (p == c->rank) continue;
             const insitu_ctx* q = c->group->ranks[p];
             if (!q) return fail(c, -1, "insitu_exchange: local group rank " + std::to_string(p) + " missing");
-            if (!q->rendered || !q->ev_valid[1]) return fail(c, -1, "insitu_exchange: local group rank " + std::to_string(p) + " has not rendered");
+            if (!q->cur->rendered || !q->cur->ev_valid[EvRenderEnd]) return fail(c, -1, "insitu_exchange: local group rank " + std::to_string(p) + " has not rendered");
             // the peer's render runs on its own stream (and maybe device): order my copies after it
-            HIPCHK(c, hipStreamWaitEvent(c->stream, q->ev[1], 0));
+            HIPCHK(c, hipStreamWaitEvent(c->stream, q->cur->ev[EvRenderEnd], 0));
             const size_t n = (size_t)c->B * c->plainBlock;
             const size_t src = (size_t)c->rank * n, dst = (size_t)p * n;
             HIPCHK(c, hipMemcpyAsync(c->d_pcol_recv + dst, q->d_pcol_send + src, n * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -1278,9 +1247,9 @@ int insitu_exchange(insitu_ctx* c) {
         NCCLCHK(c, ncclGroupEnd());
         c->last_exchange_bytes = (long long)(c->N - 1) * (long long)c->B * (long long)c->plainBlock * 8;
     }
-    if (c->group) record(c, 7);
-    record(c, 2);
-    c->exchanged = true;
+    if (c->group) record(c, EvPeerReadsDone);
+    record(c, EvExchangeEnd);
+    c->cur->exchanged = true;
     return 0;
 }
 
@@ -1291,16 +1260,16 @@ VdiList list_of(const insitu_ctx* c, int v) {
     VdiList L{};
     if (c->lists_from_reference) {   // host-buffer path: reference layout converted to slots (B == 1)
         const size_t slot = (size_t)s * c->blockE;
-        L.col = (s == c->rank ? c->d_vcol_send : c->d_vcol_recv) + slot;
-        L.dep = (s == c->rank ? c->d_vdep_send : c->d_vdep_recv) + slot;
+        L.col = (s == c->rank ? c->cur->vcol_send : c->d_vcol_recv) + slot;
+        L.dep = (s == c->rank ? c->cur->vdep_send : c->d_vdep_recv) + slot;
         L.cnt16 = c->d_ref_cnt + (size_t)s * c->stripPx;
         L.cnt_pitch = c->strip_w;
         L.cnt_x0 = 0;
     } else if (s == c->rank) {       // my own strip: the generator's slots and counts
         const size_t e = ((size_t)c->rank * (size_t)c->BV + (size_t)b) * c->blockE;
-        L.col = c->d_vcol_send + e;
-        L.dep = c->d_vdep_send + e;
-        L.cnt16 = c->d_seg_pending + (size_t)b * (size_t)c->W * (size_t)c->H;
+        L.col = c->cur->vcol_send + e;
+        L.dep = c->cur->vdep_send + e;
+        L.cnt16 = c->cur->seg_pending + (size_t)b * (size_t)c->W * (size_t)c->H;
         L.cnt_pitch = c->W;
         L.cnt_x0 = c->rank * c->strip_w;
     } else {                         // the compact message source s sent
@@ -1320,10 +1289,10 @@ int insitu_composite(insitu_ctx* c) {
     if (!c) return fail(nullptr, -1, "insitu_composite: null context");
     if (c->pipe_inflight && !c->completing)
         return fail(c, -1, "insitu_composite: a pipelined frame is in flight (insitu_pipeline_flush first)");
-    if (!c->rendered) return fail(c, -1, "insitu_composite: nothing rendered");
+    if (!c->cur->rendered) return fail(c, -1, "insitu_composite: nothing rendered");
     // with N > 1 the peers' lists arrive in insitu_exchange: without it the compact-message offsets
     // of the receive buffers are not this frame's (or never written)
-    if (c->N > 1 && !c->exchanged) return fail(c, -1, "insitu_composite: call insitu_exchange first (nranks > 1)");
+    if (c->N > 1 && !c->cur->exchanged) return fail(c, -1, "insitu_composite: call insitu_exchange first (nranks > 1)");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, wait_peer_reads(c));   // (local group: the root's gather of the last strip)
     uint32_t* out = is_root(c) ? c->d_gather + (size_t)c->rank * c->stripPx : c->d_strip;
@@ -1331,7 +1300,7 @@ int insitu_composite(insitu_ctx* c) {
         CompositeParams p{};   // VDICompositor.comp (DistributedVolumes.kt:424-439)
         p.V = c->V; p.S = c->S; p.S_out = c->S_out; p.H = c->H; p.W = c->W;
         p.strip_w = c->strip_w; p.strip_tiles = c->strip_tiles; p.x_offset = c->rank * c->strip_w;
-        std::memcpy(p.ipv, c->ipv, sizeof p.ipv);
+        std::memcpy(p.ipv, c->cur->ipv, sizeof p.ipv);
         for (int v = 0; v < c->V; ++v) p.lists[v] = list_of(c, v);
         p.out_color = cvdi_col(c);
         p.out_depth = cvdi_dep(c);
@@ -1378,7 +1347,7 @@ int insitu_composite(insitu_ctx* c) {
         FlattenParams p{};
         p.V = c->V; p.S = c->S; p.H = c->H; p.W = c->W;
         p.strip_w = c->strip_w; p.strip_tiles = c->strip_tiles; p.x_offset = c->rank * c->strip_w;
-        std::memcpy(p.ipv, c->ipv, sizeof p.ipv);
+        std::memcpy(p.ipv, c->cur->ipv, sizeof p.ipv);
         for (int v = 0; v < c->V; ++v) p.lists[v] = list_of(c, v);
         p.out = out;
         HIPCHK(c, launch_vdi_flatten(p, c->stream));
@@ -1403,8 +1372,8 @@ int insitu_composite(insitu_ctx* c) {
         p.out = out;
         HIPCHK(c, launch_plain_composite(p, c->stream));
     }
-    record(c, 3);
-    c->composited = true;
+    record(c, EvCompositeEnd);
+    c->cur->composited = true;
     return 0;
 }
 
@@ -1412,15 +1381,15 @@ int insitu_gather(insitu_ctx* c, void* host_out, size_t cap) {
     if (!c) return fail(nullptr, -1, "insitu_gather: null context");
     if (c->pipe_inflight && !c->completing)
         return fail(c, -1, "insitu_gather: a pipelined frame is in flight (insitu_pipeline_flush first)");
-    if (!c->composited) return fail(c, -1, "insitu_gather: nothing composited");
+    if (!c->cur->composited) return fail(c, -1, "insitu_gather: nothing composited");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (c->N > 1 && c->group) {   // in-process: the root pulls every peer's strip
         if (is_root(c)) {
             for (int p = 1; p < c->N; ++p) {
                 const insitu_ctx* q = c->group->ranks[p];
                 if (!q) return fail(c, -1, "insitu_gather: local group rank " + std::to_string(p) + " missing");
-                if (!q->composited || !q->ev_valid[3]) return fail(c, -1, "insitu_gather: local group rank " + std::to_string(p) + " has not composited");
-                HIPCHK(c, hipStreamWaitEvent(c->stream, q->ev[3], 0));   // the peer's composite, its stream
+                if (!q->cur->composited || !q->cur->ev_valid[EvCompositeEnd]) return fail(c, -1, "insitu_gather: local group rank " + std::to_string(p) + " has not composited");
+                HIPCHK(c, hipStreamWaitEvent(c->stream, q->cur->ev[EvCompositeEnd], 0));   // the peer's composite, its stream
                 if (c->composite_vdi) {
                     HIPCHK(c, hipMemcpyAsync(c->d_gvdi_col + (size_t)p * c->cblockE, q->d_cvdi_col, c->cblockE * sizeof(float4),
                                              hipMemcpyDeviceToDevice, c->stream));
@@ -1467,7 +1436,7 @@ int insitu_gather(insitu_ctx* c, void* host_out, size_t cap) {
             FlattenParams f{};
             f.V = 1; f.S = c->S_out; f.H = c->H; f.W = c->W;
             f.strip_w = c->strip_w; f.strip_tiles = c->strip_tiles; f.x_offset = p * c->strip_w;
-            std::memcpy(f.ipv, c->ipv, sizeof f.ipv);
+            std::memcpy(f.ipv, c->cur->ipv, sizeof f.ipv);
             f.lists[0].col = c->d_gvdi_col + (size_t)p * c->cblockE;
             f.lists[0].dep = c->d_gvdi_dep + (size_t)p * c->cblockE;
             f.lists[0].cnt16 = c->d_gvdi_cnt + (size_t)p * c->stripPx;   // (slots past the count: not written)
@@ -1479,16 +1448,16 @@ int insitu_gather(insitu_ctx* c, void* host_out, size_t cap) {
     }
     if (is_root(c) && c->mode == INSITU_MODE_VDI)
         HIPCHK(c, launch_assemble_columns(c->d_gather, c->N, c->H, c->strip_w, c->d_image, c->stream));
-    if (c->group && is_root(c)) record(c, 7);
-    record(c, 4);
+    if (c->group && is_root(c)) record(c, EvPeerReadsDone);
+    record(c, EvGatherEnd);
     if (is_root(c) && host_out) {
         const size_t bytes = (size_t)c->W * (size_t)c->H * 4;
         if (cap < bytes) return fail(c, -1, "insitu_gather: output buffer too small");
         const void* src = c->mode == INSITU_MODE_VDI ? (const void*)c->d_image : (const void*)c->d_gather;
         HIPCHK(c, hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, c->stream));
-        record(c, 10);
+        record(c, EvImageOnHost);
     } else {
-        c->ev_valid[10] = false;
+        c->cur->ev_valid[EvImageOnHost] = false;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return check_fault(c);
@@ -1515,8 +1484,7 @@ int pipeline_setup(insitu_ctx* c) {
     HIPCHK(c, hipStreamCreateWithPriority(&c->pipe_comp, hipStreamNonBlocking, hi));
     // a search stream per slot: frame k+1's search starts as soon as its first pass is done, beside frame k's
     // search tail and finish (one stream would order it after them)
-    HIPCHK(c, hipStreamCreateWithFlags(&c->slot_search_stream, hipStreamNonBlocking));
-    HIPCHK(c, hipStreamCreateWithFlags(&c->alt.search_stream, hipStreamNonBlocking));
+    for (FrameSlot& f : c->slots) HIPCHK(c, hipStreamCreateWithFlags(&f.search_stream, hipStreamNonBlocking));
     int can_wait = 0;
     if (hipDeviceGetAttribute(&can_wait, hipDeviceAttributeCanUseStreamWaitValue, c->cfg.device) != hipSuccess) can_wait = 0;
     c->pipe_wait_value = can_wait != 0;
@@ -1525,8 +1493,8 @@ int pipeline_setup(insitu_ctx* c) {
         HIPCHK(c, hipMemset(c->pipe_flag, 0, 2 * sizeof(unsigned long long)));
     }
     // the second slot starts with the cache size the first one has reached
-    if (int rc = alloc_slot(c, c->alt, c->cache_chunks)) return rc;
-    c->alt.cache_sized = c->cache_sized;
+    if (int rc = alloc_slot(c, c->slots[1], c->slots[0].cache_chunks)) return rc;
+    c->slots[1].cache_sized = c->slots[0].cache_sized;
     c->pipe_ready = true;
     return 0;
 }
@@ -1537,7 +1505,7 @@ int pipeline_complete(insitu_ctx* c, void* host_out, size_t cap) {
     StreamScope scope(c, c->pipe_comp);
     c->completing = true;
     int rc = 0;
-    if (c->ev_valid[1] && hipStreamWaitEvent(c->stream, c->ev[1], 0) != hipSuccess)
+    if (c->cur->ev_valid[EvRenderEnd] && hipStreamWaitEvent(c->stream, c->cur->ev[EvRenderEnd], 0) != hipSuccess)
         rc = fail(c, -3, "insitu_frame_pipelined: hipStreamWaitEvent failed");
     if (!rc && c->N > 1) {
         hipError_t e = compact_enqueue(c);
@@ -1546,7 +1514,7 @@ int pipeline_complete(insitu_ctx* c, void* host_out, size_t cap) {
     if (!rc) rc = insitu_exchange(c);
     if (!rc) rc = insitu_composite(c);
     if (!rc) {
-        record(c, 11);   // (recorded before gather's synchronisation: the slot may be rendered into after it)
+        record(c, EvSlotFree);   // (recorded before gather's synchronisation: the slot may be rendered into after it)
         rc = insitu_gather(c, host_out, cap);
     }
     c->completing = false;
@@ -1560,12 +1528,12 @@ int insitu_frame_pipelined(insitu_ctx* c, const insitu_camera* cam, void* host_o
     if (done_frame) *done_frame = -1;
     if (c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_frame_pipelined: VDI mode only");
     if (c->group) return fail(c, -1, "insitu_frame_pipelined: not with a local group (stages run rank by rank)");
-    if (!c->d_cache) return fail(c, -1, "insitu_frame_pipelined: needs the sample cache (sample_cache_mb >= 0)");
+    if (!c->cur->cache) return fail(c, -1, "insitu_frame_pipelined: needs the sample cache (sample_cache_mb >= 0)");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (int rc = pipeline_setup(c)) return rc;
-    // 1. frame k into the current slot (its last frame is completed: ev[11] was synchronised)
+    // 1. frame k into the current slot (its last frame is completed: EvSlotFree was synchronised)
     hipStream_t ss = c->pipe_sample;
-    if (c->ev_valid[11]) HIPCHK(c, hipStreamWaitEvent(ss, c->ev[11], 0));
+    if (c->cur->ev_valid[EvSlotFree]) HIPCHK(c, hipStreamWaitEvent(ss, c->cur->ev[EvSlotFree], 0));
     // everything enqueued on `stream` before this call -- brick ingests (a re-ingest behind the frame in flight
     // waits for that frame's search), LUT uploads, and before the first pipelined frame whatever the context did
     // unpipelined -- is ordered before this frame's first pass: the sampling stream is not `stream`
@@ -1578,10 +1546,10 @@ int insitu_frame_pipelined(insitu_ctx* c, const insitu_camera* cam, void* host_o
         int mode = c->pipe_trigger;
         if (mode == 1 && !c->pipe_wait_value) mode = 0;
         if (mode == 1) {
-            c->trig_flag = c->pipe_flag + c->alt.flag_index;
+            c->trig_flag = c->pipe_flag + c->alt->flag_index;
             c->trig_value = c->pipe_seq;
-        } else if (mode == 0 && c->alt.ev_valid[13]) {
-            c->trig_event = c->alt.ev[13];
+        } else if (mode == 0 && c->alt->ev_valid[EvSearchEnd]) {
+            c->trig_event = c->alt->ev[EvSearchEnd];
         }
     }
     c->pipe_seq++;
@@ -1620,14 +1588,16 @@ int insitu_synchronize(insitu_ctx* c) {
     if (!c) return fail(nullptr, -1, "insitu_synchronize: null context");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (hipStream_t st : {c->pipe_sample, c->pipe_comp, c->slot_search_stream, c->alt.search_stream})
+    for (hipStream_t st : {c->pipe_sample, c->pipe_comp})
         if (st) HIPCHK(c, hipStreamSynchronize(st));
+    for (FrameSlot& f : c->slots)
+        if (f.search_stream) HIPCHK(c, hipStreamSynchronize(f.search_stream));
     if (c->dbg_pending) {   // diagnostics: the last render's per-round search timing, all launches
         c->dbg_pending = false;
         std::vector<unsigned long long> h(c->dbg_entries * 4);
         GenCounters gc{};
         HIPCHK(c, hipMemcpy(h.data(), c->d_dbg, h.size() * 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(&gc, c->d_counters, sizeof gc, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&gc, c->cur->counters, sizeof gc, hipMemcpyDeviceToHost));
         if (FILE* f = std::fopen(c->dbg_path.c_str(), "wb")) {   // sizeof counters, counters, the non-empty entries
             const uint32_t hdr = (uint32_t)sizeof gc;
             std::fwrite(&hdr, sizeof hdr, 1, f);
@@ -1647,7 +1617,7 @@ size_t insitu_buffer_bytes(const insitu_ctx* c, int which) {
     case INSITU_BUF_VDI_COLOR: return c->mode == INSITU_MODE_VDI ? px * (size_t)c->S * 16 : 0;
     case INSITU_BUF_VDI_DEPTH: return c->mode == INSITU_MODE_VDI ? px * (size_t)c->S * 8 : 0;
     case INSITU_BUF_OCTREE: return c->mode == INSITU_MODE_VDI ? (size_t)c->ncx * c->ncy * c->S * 4 : 0;
-    case INSITU_BUF_PASSES: return (c->mode == INSITU_MODE_VDI && c->d_passes) ? px : 0;
+    case INSITU_BUF_PASSES: return (c->mode == INSITU_MODE_VDI && c->cur->passes) ? px : 0;
     case INSITU_BUF_PLAIN_COLOR:
     case INSITU_BUF_PLAIN_DEPTH: return c->mode == INSITU_MODE_PLAIN ? px * 4 : 0;
     case INSITU_BUF_STRIP: return c->stripPx * 4;
@@ -1657,8 +1627,8 @@ size_t insitu_buffer_bytes(const insitu_ctx* c, int which) {
     case INSITU_BUF_GATHERED_COLOR: return (c->composite_vdi && is_root(c)) ? px * (size_t)c->S_out * 16 : 0;
     case INSITU_BUF_GATHERED_DEPTH: return (c->composite_vdi && is_root(c)) ? px * (size_t)c->S_out * 8 : 0;
     case INSITU_BUF_COMPOSITE_PASSES: return c->composite_vdi ? c->stripPx : 0;
-    case INSITU_BUF_RECEIVED_COLOR: return (c->mode == INSITU_MODE_VDI && c->exchanged) ? (size_t)c->V * c->stripPx * c->S * 16 : 0;
-    case INSITU_BUF_RECEIVED_DEPTH: return (c->mode == INSITU_MODE_VDI && c->exchanged) ? (size_t)c->V * c->stripPx * c->S * 8 : 0;
+    case INSITU_BUF_RECEIVED_COLOR: return (c->mode == INSITU_MODE_VDI && c->cur->exchanged) ? (size_t)c->V * c->stripPx * c->S * 16 : 0;
+    case INSITU_BUF_RECEIVED_DEPTH: return (c->mode == INSITU_MODE_VDI && c->cur->exchanged) ? (size_t)c->V * c->stripPx * c->S * 8 : 0;
     default: return 0;
     }
 }
@@ -1676,6 +1646,7 @@ int insitu_read(insitu_ctx* c, int which, int slot, void* host_out, size_t cap) 
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (int rc = check_fault(c)) return rc;
+    const FrameSlot& f = *c->cur;
     switch (which) {
     case INSITU_BUF_VDI_COLOR:
     case INSITU_BUF_VDI_DEPTH: {
@@ -1687,7 +1658,7 @@ int insitu_read(insitu_ctx* c, int which, int slot, void* host_out, size_t cap) 
             (void)hipFree(rc);
             return fail(c, -5, "insitu_read: scratch allocation failed");
         }
-        hipError_t e = launch_vdi_to_reference(c->d_vcol_send, c->d_vdep_send, c->d_seg_pending,
+        hipError_t e = launch_vdi_to_reference(f.vcol_send, f.vdep_send, f.seg_pending,
                                                (size_t)c->W * (size_t)c->H, (size_t)c->strip_w, (size_t)c->W, c->W, 0, c->W,
                                                c->H, c->S, c->strip_w, c->strip_tiles, c->BV, slot, rc, rd, c->stream);
         if (e == hipSuccess)
@@ -1700,10 +1671,10 @@ int insitu_read(insitu_ctx* c, int which, int slot, void* host_out, size_t cap) 
         return 0;
     }
     case INSITU_BUF_OCTREE:
-        HIPCHK(c, hipMemcpy(host_out, c->d_octree + (size_t)slot * (need / 4), need, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(host_out, f.octree + (size_t)slot * (need / 4), need, hipMemcpyDeviceToHost));
         return 0;
     case INSITU_BUF_PASSES:
-        HIPCHK(c, hipMemcpy(host_out, c->d_passes + (size_t)slot * need, need, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(host_out, f.passes + (size_t)slot * need, need, hipMemcpyDeviceToHost));
         return 0;
     case INSITU_BUF_PLAIN_COLOR:
     case INSITU_BUF_PLAIN_DEPTH: {
@@ -1798,12 +1769,12 @@ int insitu_read_region(insitu_ctx* c, int which, int slot, int x0, int x1, void*
     const size_t n = nx * (size_t)c->H * (size_t)c->S;
     const size_t need = which == INSITU_BUF_VDI_COLOR ? n * 16 : (which == INSITU_BUF_VDI_DEPTH ? n * 8 : nx * (size_t)c->H);
     if (cap < need) return fail(c, -1, "insitu_read_region: output buffer too small");
-    if (which == INSITU_BUF_PASSES && !c->d_passes) return fail(c, -1, "insitu_read_region: context keeps no pass counts");
+    if (which == INSITU_BUF_PASSES && !c->cur->passes) return fail(c, -1, "insitu_read_region: context keeps no pass counts");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (int rc = check_fault(c)) return rc;
     if (which == INSITU_BUF_PASSES) {   // (H, x1-x0) rows of the (H, W) pass counts
-        HIPCHK(c, hipMemcpy2D(host_out, nx, c->d_passes + (size_t)slot * (size_t)c->W * (size_t)c->H + (size_t)x0,
+        HIPCHK(c, hipMemcpy2D(host_out, nx, c->cur->passes + (size_t)slot * (size_t)c->W * (size_t)c->H + (size_t)x0,
                               (size_t)c->W, nx, (size_t)c->H, hipMemcpyDeviceToHost));
         return 0;
     }
@@ -1818,7 +1789,7 @@ int insitu_read_region(insitu_ctx* c, int which, int slot, int x0, int x1, void*
     if (e == hipSuccess) {
         if (!rc_) rc_ = (float4*)other;
         else rd_ = (float*)other;
-        e = launch_vdi_to_reference(c->d_vcol_send, c->d_vdep_send, c->d_seg_pending, (size_t)c->W * (size_t)c->H,
+        e = launch_vdi_to_reference(c->cur->vcol_send, c->cur->vdep_send, c->cur->seg_pending, (size_t)c->W * (size_t)c->H,
                                     (size_t)c->strip_w, (size_t)c->W, c->W, x0, (int)nx, c->H, c->S, c->strip_w,
                                     c->strip_tiles, c->BV, slot, rc_, rd_, c->stream);
     }
@@ -1837,71 +1808,55 @@ int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     cache_observe(c);
     std::memset(out, 0, sizeof *out);
-    float* slots[4] = {&out->ms_render, &out->ms_exchange, &out->ms_composite, &out->ms_gather};
-    for (int i = 0; i < 4; ++i) {
-        if (c->ev_valid[i] && c->ev_valid[i + 1]) {
-            float ms = 0.0f;
-            if (hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]) == hipSuccess) *slots[i] = ms;
-        }
-    }
-    if (c->ev_valid[4] && c->ev_valid[10]) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->ev[4], c->ev[10]) == hipSuccess) out->ms_image_d2h = ms;
-    }
-    out->cache_bytes = (long long)c->cache_chunks * 32;
+    const FrameSlot& f = *c->cur;
+    // the time from event a to event b of the slot's frame, when both were recorded
+    auto span = [&f](int a, int b, float* ms) {
+        return f.ev_valid[a] && f.ev_valid[b] && hipEventElapsedTime(ms, f.ev[a], f.ev[b]) == hipSuccess;
+    };
+    const bool vdi_ranks = c->mode == INSITU_MODE_VDI && c->N > 1;
+    float ms = 0.0f;
+    float* stages[4] = {&out->ms_render, &out->ms_exchange, &out->ms_composite, &out->ms_gather};
+    for (int i = EvRenderStart; i < EvGatherEnd; ++i)   // (the stage events are consecutive, FrameEvent)
+        if (span(i, i + 1, &ms)) *stages[i] = ms;
+    if (span(EvGatherEnd, EvImageOnHost, &ms)) out->ms_image_d2h = ms;
+    out->cache_bytes = (long long)f.cache_chunks * 32;
     out->exchange_bytes = c->last_exchange_bytes;
     out->exchange_entries = c->last_exchange_entries;
-    if (c->mode == INSITU_MODE_VDI && c->d_counters) {
+    if (c->mode == INSITU_MODE_VDI && f.counters) {
         // the render's pinned copy when it has arrived: a synchronous copy out of device memory is a blit kernel,
         // and with a pipelined frame's persistent search holding every CU it waited ~2 ms for a slot (the 8-GPU
         // share's trace: the host's next frame call, and so the next first pass, came that much late)
         GenCounters gc{};
-        if (c->h_ctr_valid) gc = *c->h_ctr;
-        else HIPCHK(c, hipMemcpy(&gc, c->d_counters, sizeof gc, hipMemcpyDeviceToHost));
+        if (f.h_ctr_valid) gc = *f.h_ctr;
+        else HIPCHK(c, hipMemcpy(&gc, f.counters, sizeof gc, hipMemcpyDeviceToHost));
         out->rays_searched = (long long)gc.queue_count + (long long)gc.queue_short;
         out->rays_uncached = (long long)gc.march_rays + (long long)gc.cap_overflow;
         out->cache_demand_bytes = (long long)gc.cache_cursor * 32;
         out->search_regroups = (int)gc.regroups;
     }
-    if (c->mode == INSITU_MODE_VDI && c->N > 1 && c->ev_valid[8] && c->ev_valid[9]) {
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->ev[8], c->ev[9]) == hipSuccess) out->ms_exchange_sync = ms;
-    }
-    if (c->mode == INSITU_MODE_VDI && c->N > 1 && c->ev_valid[6] && c->ev_valid[12]) {   // compaction: exchange
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->ev[6], c->ev[12]) == hipSuccess) {
-            out->ms_compact = ms;
-            if (!c->slot_pipelined) {   // (a pipelined frame packs after its render, in its exchange span)
-                out->ms_render -= ms;
-                out->ms_exchange += ms;
-            }
+    if (vdi_ranks && span(EvCountsIn, EvPayloadStart, &ms)) out->ms_exchange_sync = ms;
+    if (vdi_ranks && span(EvCompactStart, EvCompactEnd, &ms)) {   // compaction: exchange
+        out->ms_compact = ms;
+        if (!f.pipelined) {   // (a pipelined frame packs after its render, in its exchange span)
+            out->ms_render -= ms;
+            out->ms_exchange += ms;
         }
     }
-    if (c->slot_pipelined && c->ev_valid[1] && c->ev_valid[6] && c->N > 1) {   // exchange from its compaction
-        float ms = 0.0f;
-        if (c->ev_valid[2] && hipEventElapsedTime(&ms, c->ev[6], c->ev[2]) == hipSuccess) out->ms_exchange = ms;
-    }
-    {   // latency: render start to the image on the host (or the gather's end)
-        const int end = c->ev_valid[10] ? 10 : 4;
-        float ms = 0.0f;
-        if (c->ev_valid[0] && c->ev_valid[end] && hipEventElapsedTime(&ms, c->ev[0], c->ev[end]) == hipSuccess)
-            out->ms_latency = ms;
-    }
-    out->pipelined = c->slot_pipelined ? 1 : 0;
-    {   // the last batch of re-ingests, once it is done (a pipelined loop does not wait for it)
-        float ms = 0.0f;
-        if (hipEventQuery(c->ev_ingest) == hipSuccess && hipEventElapsedTime(&ms, c->ev_ingest0, c->ev_ingest) == hipSuccess)
-            out->ms_ingest = ms;
-        (void)hipGetLastError();
-    }
+    if (f.pipelined && f.ev_valid[EvRenderEnd] && c->N > 1 && span(EvCompactStart, EvExchangeEnd, &ms))
+        out->ms_exchange = ms;   // exchange from its compaction
+    // latency: render start to the image on the host (or the gather's end)
+    if (span(EvRenderStart, f.ev_valid[EvImageOnHost] ? EvImageOnHost : EvGatherEnd, &ms)) out->ms_latency = ms;
+    out->pipelined = f.pipelined ? 1 : 0;
+    // the last batch of re-ingests, once it is done (a pipelined loop does not wait for it)
+    if (hipEventQuery(c->ev_ingest) == hipSuccess && hipEventElapsedTime(&ms, c->ev_ingest0, c->ev_ingest) == hipSuccess)
+        out->ms_ingest = ms;
+    (void)hipGetLastError();
     out->ms_sample = out->ms_render;
-    if (c->mode == INSITU_MODE_VDI && c->ev_valid[5] && c->ev_valid[0] && c->ev_valid[1]) {
-        float a = 0.0f, b = 0.0f;
-        if (hipEventElapsedTime(&a, c->ev[0], c->ev[5]) == hipSuccess &&
-            hipEventElapsedTime(&b, c->ev[5], c->ev[1]) == hipSuccess) {
-            out->ms_sample = a;
-            out->ms_search = b - out->ms_compact;
-        }
+    float a = 0.0f, b = 0.0f;
+    if (c->mode == INSITU_MODE_VDI && f.ev_valid[EvRenderEnd] && span(EvRenderStart, EvSampleEnd, &a) &&
+        span(EvSampleEnd, EvRenderEnd, &b)) {
+        out->ms_sample = a;
+        out->ms_search = b - out->ms_compact;
     }
     return 0;
 }
@@ -1909,11 +1864,11 @@ int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
 int insitu_pass_stats(insitu_ctx* c, double* mean_passes, long long* rays_hit) {
     if (!c || !mean_passes || !rays_hit) return fail(c, -1, "insitu_pass_stats: null argument");
     StreamScope scope(c, read_stream(c));   // (a pipelined frame in flight: the completed frame's slot)
-    if (!c->d_passes || c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_pass_stats: needs VDI mode + keep_passes");
+    if (!c->cur->passes || c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_pass_stats: needs VDI mode + keep_passes");
     HIPCHK(c, hipSetDevice(c->cfg.device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<uint8_t> h((size_t)c->BV * (size_t)c->W * (size_t)c->H);
-    HIPCHK(c, hipMemcpy(h.data(), c->d_passes, h.size(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(h.data(), c->cur->passes, h.size(), hipMemcpyDeviceToHost));
     long long hit = 0, sum = 0;
     for (uint8_t v : h)
         if (v) { ++hit; sum += v; }
@@ -1937,7 +1892,7 @@ int insitu_distribute_vdis(insitu_ctx* c, const void* subVDIColor, const void* s
         const size_t bytes = (size_t)c->N * c->plainBlock * 4;
         HIPCHK(c, hipMemcpyAsync(c->d_pcol_send, subVDIColor, bytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_pdep_send, subVDIDepth, bytes, hipMemcpyHostToDevice, c->stream));
-        c->rendered = true;
+        c->cur->rendered = true;
         int rc = insitu_exchange(c);
         if (rc) return rc;
         for (int s = 0; s < c->N; ++s) {   // the received set, source-major (compositeVDIs' VDISetColour)
@@ -1990,14 +1945,14 @@ int insitu_distribute_vdis(insitu_ctx* c, const void* subVDIColor, const void* s
     // uploadForCompositing (DistributedVolumes.kt:945-998): the received set feeds the compositor
     for (int s = 0; s < c->N; ++s) {
         const size_t slot = s == c->rank ? (size_t)c->rank * c->blockE : (size_t)s * c->blockE;
-        float4* dc = (s == c->rank ? c->d_vcol_send : c->d_vcol_recv) + slot;
-        float2* dd = (s == c->rank ? c->d_vdep_send : c->d_vdep_recv) + slot;
+        float4* dc = (s == c->rank ? c->cur->vcol_send : c->d_vcol_recv) + slot;
+        float2* dd = (s == c->rank ? c->cur->vdep_send : c->d_vdep_recv) + slot;
         HIPCHK(c, launch_vdi_from_reference(recv_c + (size_t)s * blkE, recv_d + (size_t)s * 2 * blkE, c->H, c->S,
                                             c->strip_w, c->strip_tiles, dc, dd, c->d_ref_cnt + (size_t)s * c->stripPx,
                                             c->stream));
     }
-    c->rendered = true;
-    c->exchanged = true;
+    c->cur->rendered = true;
+    c->cur->exchanged = true;
     c->lists_from_reference = true;
     int rc = insitu_composite(c);
     if (rc) return rc;
