@@ -15,7 +15,9 @@
  * insitu_exchange replaces distributeVDIs' MPI_Alltoall (RCCL over xGMI, device buffers),
  * insitu_composite replaces the compositor dispatch (PlainImageCompositor.comp, or the VDI
  * flatten of VDIGenerator.comp:147-185 in VDICompositor.comp:58-91 order), and
- * insitu_gather replaces gatherCompositedVDIs' MPI_Gather.  The reference-shaped entry
+ * insitu_gather replaces gatherCompositedVDIs' MPI_Gather.  insitu_view_bind / insitu_view_render
+ * render the last completed VDI from any other camera (the consumer the VDI exists for: the
+ * reference's EfficientVDIRaycast.comp).  The reference-shaped entry
  * points at the bottom keep the exact Kotlin argument lists for a JNI shim
  * (INTEGRATION.md).
  *
@@ -32,7 +34,7 @@
 extern "C" {
 #endif
 
-#define INSITU_ABI_VERSION 8
+#define INSITU_ABI_VERSION 9
 #define INSITU_COMM_ID_BYTES 128
 
 typedef struct insitu_ctx insitu_ctx;
@@ -69,7 +71,16 @@ enum insitu_buf {
      * empty slots zero: what allToAllColorPointer holds and uploadForCompositing receives
      * (DistributedVolumes.kt:945), dumped as SetOfVDI{n}_ndc_col / _ndc_depth (:974-975)        */
     INSITU_BUF_RECEIVED_COLOR = 13,
-    INSITU_BUF_RECEIVED_DEPTH = 14
+    INSITU_BUF_RECEIVED_DEPTH = 14,
+    /* after insitu_view_render: the view of the bound VDI from the last viewing camera */
+    INSITU_BUF_VIEW_COLOR = 15,  /* (out_h,out_w) rgba32f, the front-to-back accumulator           */
+    INSITU_BUF_VIEW_IMAGE = 16   /* (out_h,out_w) rgba8                                            */
+};
+
+/* What insitu_view_bind takes its VDI from. */
+enum insitu_view_source {
+    INSITU_VIEW_GATHERED = 0, /* root of a composite_vdi context: the gathered composited VDI (W,H,S_out) */
+    INSITU_VIEW_BRICK = 1     /* brick `slot`'s sub-VDI (W,H,S)                                             */
 };
 
 typedef struct insitu_config {
@@ -152,6 +163,7 @@ typedef struct insitu_stats {
                                     at its trigger: its prepare was queued ahead of it)   */
     float ms_ingest;             /* GPU time of the last batch of insitu_set_brick re-ingests (the bricks set
                                     between two renders; 0 until one has completed)                     */
+    float ms_view;               /* GPU time of the last insitu_view_render's kernel (0 until one has run)  */
 } insitu_stats;
 
 /* Tuning and diagnostics options (insitu_set_option); the defaults are the measured optimum. */
@@ -178,10 +190,13 @@ enum insitu_option {
     INSITU_OPT_PIPE_OVERSUB = 12,  /* 1..64: INSITU_OPT_SEARCH_OVERSUB of pipelined frames (default 3; their
                                       search shares the GPU with the next frame's first pass, so fewer
                                       speculative tree lanes pay: DESIGN.md 5.1)                          */
-    INSITU_OPT_PIPE_SEARCH_RAYS = 13 /* pipelined frames: queued rays per searching block of the threshold
+    INSITU_OPT_PIPE_SEARCH_RAYS = 13, /* pipelined frames: queued rays per searching block of the threshold
                                       search, which then keeps one to two blocks per CU and leaves the other
                                       wave slots to the next frame's first pass (default 2048; 0 = the full
                                       persistent grid, as unpipelined frames)                              */
+    INSITU_OPT_VIEW_SKIP = 14      /* insitu_view_render: 1 (default): an 8x8 tile of lists whose largest count
+                                      is 0 is stepped over in one step; 0: every cell is walked -- identical
+                                      results                                                */
 };
 
 int insitu_abi_version(void);
@@ -238,10 +253,28 @@ size_t insitu_buffer_bytes(const insitu_ctx* ctx, int which);
  * rgba32f, INSITU_BUF_VDI_DEPTH (x1-x0, H, 2S) r32f (x slowest, as (S,H,W) images), or
  * INSITU_BUF_PASSES (H, x1-x0) uint8 -- parity checks of frames too large to read whole. */
 int insitu_read_region(insitu_ctx* ctx, int which, int slot, int x0, int x1, void* host_out, size_t cap);
+/* ---- novel-view rendering of a VDI ----
+ * insitu_view_bind takes a snapshot of a VDI of the last completed frame (enum insitu_view_source; between
+ * insitu_frame_pipelined calls the completed frame, as insitu_read) with that frame's camera as the generating
+ * camera, and blocks until the snapshot is built: later frames, pipelined ones included, do not disturb it.
+ * INSITU_VIEW_GATHERED needs a composite_vdi context, rank 0 and a gathered frame; INSITU_VIEW_BRICK a rendered
+ * frame and 0 <= slot < the context's sub-VDIs. */
+int insitu_view_bind(insitu_ctx* ctx, int source, int slot);
+/* The same from host memory: a VDI in the reference layout -- colour (W,H,S,4) rgba32f and depth (W,H,2S) r32f, x
+ * slowest, as the dumps hold it (vdi_io.read_vdi) -- with the camera that generated it.  W, H and S (1..255) need
+ * not be the context's.  A list ends before its first entry whose start depth is 0; the entries before it are
+ * trusted to be ordered by depth and not to overlap, as the generator and the compositor write them. */
+int insitu_view_bind_host(insitu_ctx* ctx, const void* color, const void* depth, int W, int H, int S,
+                          const insitu_camera* gen_cam);
+/* Render the bound VDI from `cam` at out_w x out_h and block until it is done.  host_out non-NULL: receives the
+ * (out_h,out_w) rgba8 image (cap >= out_w*out_h*4).  INSITU_BUF_VIEW_COLOR / INSITU_BUF_VIEW_IMAGE then hold the
+ * rgba32f accumulator and the image (insitu_read, insitu_buffer_bytes).  Only cam's view and projection (and its
+ * inverses) are used. */
+int insitu_view_render(insitu_ctx* ctx, const insitu_camera* cam, int out_w, int out_h, void* host_out, size_t cap);
 int insitu_get_stats(insitu_ctx* ctx, insitu_stats* out);
 /* Set a tuning option (enum insitu_option) for the following renders; -1 on an unknown option or
  * a value out of range.  Environment variables INSITU_<OPTION NAME> (INSITU_EXACT_SEARCH,
- * INSITU_SEARCH_DEPTH, ..., INSITU_PIPE_TRIGGER) seed the values when the context is created (tuning scripts). */
+ * INSITU_SEARCH_DEPTH, ..., INSITU_VIEW_SKIP) seed the values when the context is created (tuning scripts). */
 int insitu_set_option(insitu_ctx* ctx, int option, long long value);
 /* Mean raymarch passes over rays that hit a brick, and the number of such rays, of the last
  * render over all local bricks (needs keep_passes; reads the pass buffer back). */

@@ -160,6 +160,24 @@ struct FrameSlot {
     bool ev_valid[kFrameEvents] = {};
 };
 
+// The bound VDI of insitu_view_bind / insitu_view_bind_host -- a snapshot in the view layout, with its generating
+// camera -- and the output of the last insitu_view_render.  Its buffers belong to no frame slot and its work
+// runs on a stream of its own, which is idle between calls (both calls block).
+struct ViewState {
+    ViewVdi vdi{};                      // null until the first bind
+    size_t cap_entries = 0, cap_px = 0, cap_tiles = 0;   // allocated sizes (grown by a larger bind)
+    float pv_g[16] = {};                // proj * view of the generating camera
+    bool bound = false;
+    float4* out_color = nullptr;        // (out_h, out_w) rgba32f / rgba8 of the last render
+    uint32_t* out_image = nullptr;
+    size_t out_cap = 0;                 // pixels allocated
+    int out_w = 0, out_h = 0;           // of the last render (0: none yet)
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    float ms = 0.0f;                    // the last render's kernel
+    long long skip = 1;                 // INSITU_OPT_VIEW_SKIP
+};
+
 struct insitu_ctx {
     insitu_config cfg{};
     insitu_local_group* group = nullptr;   // in-process rank group (test transport), else RCCL
@@ -222,6 +240,8 @@ struct insitu_ctx {
     float2* d_cvdi_dep = nullptr;
     float4* d_gvdi_col = nullptr;       // root: gathered composited strips [rank][block]
     float2* d_gvdi_dep = nullptr;
+    bool gvdi_valid = false;            // root: a gather has filled them, from the frame of camera gvdi_pv
+    float gvdi_pv[16] = {};
     uint16_t* d_cvdi_cnt = nullptr;     // per pixel of this rank's composited strip: slots written (non-root ranks)
     uint16_t* d_gvdi_cnt = nullptr;     // root: the gathered counts [rank][y][x_local]
     uint8_t* d_cpasses = nullptr;       // compositor search passes of the strip
@@ -264,6 +284,7 @@ struct insitu_ctx {
     unsigned long long* trig_flag = nullptr;         // wait for *trig_flag >= trig_value (mode 1) ...
     unsigned long long trig_value = 0;
     hipEvent_t trig_event = nullptr;                 // ... or for this event (mode 0)
+    ViewState view;
     std::string err;
 };
 
@@ -321,6 +342,16 @@ void release(insitu_ctx* c) {
         if (st) (void)hipStreamSynchronize(st);
     for (FrameSlot& f : c->slots)
         if (f.search_stream) (void)hipStreamSynchronize(f.search_stream);
+    {
+        ViewState& v = c->view;
+        if (v.stream) (void)hipStreamSynchronize(v.stream);
+        void* vp[] = {v.vdi.col, v.vdi.dep, v.vdi.cnt, v.vdi.tmax, v.out_color, v.out_image};
+        for (void* p : vp)
+            if (p) (void)hipFree(p);
+        if (v.ev0) (void)hipEventDestroy(v.ev0);
+        if (v.ev1) (void)hipEventDestroy(v.ev1);
+        if (v.stream) (void)hipStreamDestroy(v.stream);
+    }
     for (auto& b : c->bricks)
         if (b.d) (void)hipFree(b.d);
     void* ptrs[] = {c->d_tf, c->d_cmap, c->d_vcol_recv, c->d_vdep_recv, c->d_pcol_send, c->d_pdep_send, c->d_pcol_recv, c->d_pdep_recv,
@@ -740,7 +771,8 @@ int insitu_create(const insitu_config* cfg, insitu_ctx** out) {
             {"INSITU_SEARCH_OVERSUB", INSITU_OPT_SEARCH_OVERSUB}, {"INSITU_TILE_ORDER", INSITU_OPT_TILE_ORDER},
             {"INSITU_SUPER_TILE", INSITU_OPT_SUPER_TILE}, {"INSITU_REGROUP", INSITU_OPT_REGROUP},
             {"INSITU_EXACT_TILE_KEYS", INSITU_OPT_EXACT_TILE_KEYS}, {"INSITU_PIPE_TRIGGER", INSITU_OPT_PIPE_TRIGGER},
-            {"INSITU_PIPE_OVERSUB", INSITU_OPT_PIPE_OVERSUB}, {"INSITU_PIPE_SEARCH_RAYS", INSITU_OPT_PIPE_SEARCH_RAYS}};
+            {"INSITU_PIPE_OVERSUB", INSITU_OPT_PIPE_OVERSUB}, {"INSITU_PIPE_SEARCH_RAYS", INSITU_OPT_PIPE_SEARCH_RAYS},
+            {"INSITU_VIEW_SKIP", INSITU_OPT_VIEW_SKIP}};
         for (const auto& nm : names) {
             if (const char* v = std::getenv(nm.name)) {
                 if (insitu_set_option(c, nm.opt, std::atoll(v)) != 0) {
@@ -809,7 +841,10 @@ int insitu_set_option(insitu_ctx* c, int option, long long v) {
         if (v < 0 || v > (1ll << 24)) break;
         t.pipe_search_rays = v;
         return 0;
-
+    case INSITU_OPT_VIEW_SKIP:
+        if (v != 0 && v != 1) break;
+        c->view.skip = v;
+        return 0;
     default:
         return fail(c, -1, "insitu_set_option: unknown option " + std::to_string(option));
     }
@@ -1446,6 +1481,10 @@ int insitu_gather(insitu_ctx* c, void* host_out, size_t cap) {
             HIPCHK(c, launch_vdi_flatten(f, c->stream));
         }
     }
+    if (is_root(c) && c->composite_vdi) {   // what insitu_view_bind(INSITU_VIEW_GATHERED) takes, and its camera
+        c->gvdi_valid = true;
+        std::memcpy(c->gvdi_pv, c->cur->pv, sizeof c->gvdi_pv);
+    }
     if (is_root(c) && c->mode == INSITU_MODE_VDI)
         HIPCHK(c, launch_assemble_columns(c->d_gather, c->N, c->H, c->strip_w, c->d_image, c->stream));
     if (c->group && is_root(c)) record(c, EvPeerReadsDone);
@@ -1629,6 +1668,8 @@ size_t insitu_buffer_bytes(const insitu_ctx* c, int which) {
     case INSITU_BUF_COMPOSITE_PASSES: return c->composite_vdi ? c->stripPx : 0;
     case INSITU_BUF_RECEIVED_COLOR: return (c->mode == INSITU_MODE_VDI && c->cur->exchanged) ? (size_t)c->V * c->stripPx * c->S * 16 : 0;
     case INSITU_BUF_RECEIVED_DEPTH: return (c->mode == INSITU_MODE_VDI && c->cur->exchanged) ? (size_t)c->V * c->stripPx * c->S * 8 : 0;
+    case INSITU_BUF_VIEW_COLOR: return (size_t)c->view.out_w * (size_t)c->view.out_h * 16;
+    case INSITU_BUF_VIEW_IMAGE: return (size_t)c->view.out_w * (size_t)c->view.out_h * 4;
     default: return 0;
     }
 }
@@ -1640,6 +1681,12 @@ int insitu_read(insitu_ctx* c, int which, int slot, void* host_out, size_t cap) 
     const size_t need = insitu_buffer_bytes(c, which);
     if (need == 0) return fail(c, -1, "insitu_read: buffer not available in this mode/rank");
     if (cap < need) return fail(c, -1, "insitu_read: output buffer too small");
+    if (which == INSITU_BUF_VIEW_COLOR || which == INSITU_BUF_VIEW_IMAGE) {   // (insitu_view_render blocked: ready)
+        HIPCHK(c, hipSetDevice(c->cfg.device));
+        HIPCHK(c, hipMemcpy(host_out, which == INSITU_BUF_VIEW_COLOR ? (const void*)c->view.out_color : (const void*)c->view.out_image,
+                            need, hipMemcpyDeviceToHost));
+        return 0;
+    }
     const bool per_brick = which <= INSITU_BUF_PLAIN_DEPTH;
     if (per_brick && (slot < 0 || slot >= (c->mode == INSITU_MODE_VDI ? c->BV : c->B)))
         return fail(c, -1, "insitu_read: slot out of range");
@@ -1801,6 +1848,179 @@ int insitu_read_region(insitu_ctx* c, int which, int slot, int x0, int x1, void*
     return 0;
 }
 
+namespace {
+
+// the view's stream and events (first bind), and room for a VDI of (W, H, S) in the view layout
+int view_reserve(insitu_ctx* c, int W, int H, int S) {
+    ViewState& v = c->view;
+    if (!v.stream) HIPCHK(c, hipStreamCreateWithFlags(&v.stream, hipStreamNonBlocking));
+    if (!v.ev0) HIPCHK(c, hipEventCreate(&v.ev0));
+    if (!v.ev1) HIPCHK(c, hipEventCreate(&v.ev1));
+    v.bound = false;
+    const int tx = (W + 7) / 8, ty = (H + 7) / 8;
+    const size_t px = (size_t)W * (size_t)H, entries = px * (size_t)S, tiles = (size_t)tx * (size_t)ty;
+    int rc = 0;
+    if (entries > v.cap_entries) {
+        if (v.vdi.col) (void)hipFree(v.vdi.col);
+        if (v.vdi.dep) (void)hipFree(v.vdi.dep);
+        v.vdi.col = nullptr;
+        v.vdi.dep = nullptr;
+        v.cap_entries = 0;
+        if ((rc = dev_alloc(c, &v.vdi.col, entries)) || (rc = dev_alloc(c, &v.vdi.dep, entries))) return rc;
+        v.cap_entries = entries;
+    }
+    if (px > v.cap_px) {
+        if (v.vdi.cnt) (void)hipFree(v.vdi.cnt);
+        v.vdi.cnt = nullptr;
+        v.cap_px = 0;
+        if ((rc = dev_alloc(c, &v.vdi.cnt, px))) return rc;
+        v.cap_px = px;
+    }
+    if (tiles > v.cap_tiles) {
+        if (v.vdi.tmax) (void)hipFree(v.vdi.tmax);
+        v.vdi.tmax = nullptr;
+        v.cap_tiles = 0;
+        if ((rc = dev_alloc(c, &v.vdi.tmax, tiles))) return rc;
+        v.cap_tiles = tiles;
+    }
+    v.vdi.W = W; v.vdi.H = H; v.vdi.S = S; v.vdi.tiles_x = tx; v.vdi.tiles_y = ty;
+    return 0;
+}
+
+// view_build_kernel over `src` on the view's stream; blocks until the snapshot is built
+int view_build(insitu_ctx* c, const ViewSource& src, const float* pv_g, const char* who) {
+    ViewState& v = c->view;
+    hipError_t e = launch_view_build(src, v.vdi, v.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
+    if (e != hipSuccess) return fail(c, -3, std::string(who) + ": view_build_kernel: " + hipGetErrorString(e));
+    std::memcpy(v.pv_g, pv_g, sizeof v.pv_g);
+    v.bound = true;
+    return 0;
+}
+
+}  // namespace
+
+int insitu_view_bind(insitu_ctx* c, int source, int slot) {
+    if (!c) return fail(nullptr, -1, "insitu_view_bind: null context");
+    if (c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_view_bind: VDI mode only");
+    StreamScope scope(c, read_stream(c));   // (a pipelined frame in flight: the completed frame's slot)
+    const FrameSlot& f = *c->cur;
+    ViewSource src{};
+    const float* pv = nullptr;
+    int S = 0;
+    if (source == INSITU_VIEW_GATHERED) {
+        if (!c->composite_vdi) return fail(c, -1, "insitu_view_bind: the gathered VDI needs a composite_vdi context");
+        if (!is_root(c)) return fail(c, -1, "insitu_view_bind: the gathered VDI is on rank 0 only");
+        if (!c->gvdi_valid) return fail(c, -1, "insitu_view_bind: no frame gathered yet");
+        src.col = c->d_gvdi_col; src.dep = c->d_gvdi_dep; src.cnt = c->d_gvdi_cnt;
+        src.cnt_stride = 0; src.cnt_dstride = c->stripPx; src.cnt_pitch = (size_t)c->strip_w;
+        src.B = 1; src.b = 0;
+        S = c->S_out;
+        pv = c->gvdi_pv;
+    } else if (source == INSITU_VIEW_BRICK) {
+        if (slot < 0 || slot >= c->BV) return fail(c, -1, "insitu_view_bind: slot out of range");
+        if (!f.rendered || !f.ev_valid[EvRenderEnd]) return fail(c, -1, "insitu_view_bind: no frame rendered yet");
+        src.col = f.vcol_send; src.dep = f.vdep_send; src.cnt = f.seg_pending;
+        src.cnt_stride = (size_t)c->W * (size_t)c->H; src.cnt_dstride = (size_t)c->strip_w; src.cnt_pitch = (size_t)c->W;
+        src.B = c->BV; src.b = slot;
+        S = c->S;
+        pv = f.pv;
+    } else {
+        return fail(c, -1, "insitu_view_bind: unknown source " + std::to_string(source));
+    }
+    src.strip_w = c->strip_w; src.strip_tiles = c->strip_tiles;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    // the frame's own work is done before the snapshot is taken (its render may still be running when no
+    // stage after it has synchronised)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (f.search_stream) HIPCHK(c, hipStreamSynchronize(f.search_stream));
+    if (int rc = check_fault(c)) return rc;
+    if (int rc = view_reserve(c, c->W, c->H, S)) return rc;
+    return view_build(c, src, pv, "insitu_view_bind");
+}
+
+int insitu_view_bind_host(insitu_ctx* c, const void* color, const void* depth, int W, int H, int S,
+                          const insitu_camera* gen_cam) {
+    if (!c) return fail(nullptr, -1, "insitu_view_bind_host: null context");
+    if (!color || !depth || !gen_cam) return fail(c, -1, "insitu_view_bind_host: null argument");
+    if (W <= 0 || H <= 0 || S < 1 || S > 255) return fail(c, -1, "insitu_view_bind_host: needs W, H > 0 and S in [1,255]");
+    float pv[16];
+    mat4_mul_f(gen_cam->proj, gen_cam->view, pv);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = view_reserve(c, W, H, S)) return rc;
+    const size_t n = (size_t)W * (size_t)H * (size_t)S;
+    float4* rc_ = nullptr;
+    float* rd_ = nullptr;
+    HIPCHK(c, hipMalloc(&rc_, n * sizeof(float4)));
+    if (hipMalloc(&rd_, n * 2 * sizeof(float)) != hipSuccess) {
+        (void)hipFree(rc_);
+        return fail(c, -5, "insitu_view_bind_host: staging allocation failed");
+    }
+    hipError_t e = hipMemcpyAsync(rc_, color, n * sizeof(float4), hipMemcpyHostToDevice, c->view.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rd_, depth, n * 2 * sizeof(float), hipMemcpyHostToDevice, c->view.stream);
+    int rc = 0;
+    if (e != hipSuccess) {
+        rc = fail(c, -3, std::string("insitu_view_bind_host: upload: ") + hipGetErrorString(e));
+        (void)hipStreamSynchronize(c->view.stream);
+    } else {
+        ViewSource src{};
+        src.ref_col = rc_;
+        src.ref_dep = rd_;
+        rc = view_build(c, src, pv, "insitu_view_bind_host");   // (blocks: the staging is free afterwards)
+    }
+    (void)hipFree(rc_);
+    (void)hipFree(rd_);
+    return rc;
+}
+
+int insitu_view_render(insitu_ctx* c, const insitu_camera* cam, int out_w, int out_h, void* host_out, size_t cap) {
+    if (!c) return fail(nullptr, -1, "insitu_view_render: null context");
+    if (!cam) return fail(c, -1, "insitu_view_render: null camera");
+    ViewState& v = c->view;
+    if (!v.bound) return fail(c, -1, "insitu_view_render: no VDI bound (insitu_view_bind first)");
+    if (out_w <= 0 || out_h <= 0 || (long long)out_w * (long long)out_h > (1ll << 30))
+        return fail(c, -1, "insitu_view_render: bad output size");
+    const size_t px = (size_t)out_w * (size_t)out_h;
+    if (host_out && cap < px * 4) return fail(c, -1, "insitu_view_render: output buffer too small");
+    ViewParams p{};
+    float iv[16], ip[16];
+    if (cam->has_inverses) {
+        std::memcpy(iv, cam->inv_view, sizeof iv);
+        std::memcpy(ip, cam->inv_proj, sizeof ip);
+    } else if (!mat4_inverse(cam->view, iv) || !mat4_inverse(cam->proj, ip)) {
+        return fail(c, -1, "insitu_view_render: view or projection matrix is singular");
+    }
+    mat4_mul_f(iv, ip, p.ipv_n);
+    std::memcpy(p.pv_g, v.pv_g, sizeof p.pv_g);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (px > v.out_cap) {
+        if (v.out_color) (void)hipFree(v.out_color);
+        if (v.out_image) (void)hipFree(v.out_image);
+        v.out_color = nullptr;
+        v.out_image = nullptr;
+        v.out_cap = 0;
+        v.out_w = v.out_h = 0;
+        int rc = 0;
+        if ((rc = dev_alloc(c, &v.out_color, px)) || (rc = dev_alloc(c, &v.out_image, px))) return rc;
+        v.out_cap = px;
+    }
+    p.vdi = v.vdi;
+    p.out_w = out_w; p.out_h = out_h;
+    p.skip = (int)v.skip;
+    p.out_color = v.out_color;
+    p.out_image = v.out_image;
+    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+    hipError_t e = launch_vdi_view(p, v.stream);
+    if (e != hipSuccess) return fail(c, -3, std::string("vdi_view_kernel: ") + hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(v.ev1, v.stream));
+    if (host_out) HIPCHK(c, hipMemcpyAsync(host_out, v.out_image, px * 4, hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(c, hipStreamSynchronize(v.stream));
+    v.out_w = out_w; v.out_h = out_h;
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms = ms;
+    return 0;
+}
+
 int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
     if (!c || !out) return fail(c, -1, "insitu_get_stats: null argument");
     StreamScope scope(c, read_stream(c));   // (a pipelined frame in flight: the completed frame's slot)
@@ -1851,6 +2071,7 @@ int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
     if (hipEventQuery(c->ev_ingest) == hipSuccess && hipEventElapsedTime(&ms, c->ev_ingest0, c->ev_ingest) == hipSuccess)
         out->ms_ingest = ms;
     (void)hipGetLastError();
+    out->ms_view = c->view.ms;
     out->ms_sample = out->ms_render;
     float a = 0.0f, b = 0.0f;
     if (c->mode == INSITU_MODE_VDI && f.ev_valid[EvRenderEnd] && span(EvRenderStart, EvSampleEnd, &a) &&

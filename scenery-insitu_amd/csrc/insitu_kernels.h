@@ -273,4 +273,47 @@ hipError_t launch_vdi_to_reference(const float4* color, const float2* depth, con
                                    size_t pend_dstride, size_t pend_pitch, int W, int x0, int nx, int H, int S, int strip_w,
                                    int strip_tiles, int B, int b, float4* ref_color, float* ref_depth, hipStream_t s);
 
+
+// ---- novel-view rendering of a VDI (vdi_view.hip) ----
+// View layout of a bound VDI of dimensions (W, H, S): per pixel p = y*W + x (rows y-major) a count
+// cnt[p] and the list's entries at p*S + i, i < cnt[p] -- one contiguous run per list, horizontally
+// neighbouring lists neighbours in memory; per 8x8-pixel tile (index ty*tiles_x + tx) the largest count.
+struct ViewVdi {
+    float4* col;     // W*H*S entries
+    float2* dep;     // {start, end} depth in the generating view's NDC
+    uint8_t* cnt;    // W*H
+    uint8_t* tmax;   // tiles_x*tiles_y
+    int W, H, S, tiles_x, tiles_y;
+};
+
+// What view_build_kernel reads.  Slotted (ref_col == null): the [d][b][xt][i][y][xx] blocks of the
+// generator's sub-VDIs and of the gathered composited VDI, entry of slot i of pixel (x, y) of brick b at
+// ((d*B + b)*strip_tiles*S*H*8) + ((xt*S + i)*H + y)*8 + xx with d = x / strip_w, xt = (x % strip_w) / 8,
+// and the pixel's stored count (& kPendingCount) at cnt[b*cnt_stride + d*cnt_dstride + y*cnt_pitch + x % strip_w]
+// (the parameters of launch_vdi_to_reference).  Reference layout (ref_col != null): colour (W,H,S) rgba32f and
+// depth (W,H,2S) r32f, x slowest, every slot present.  Either way a list ends before its first entry whose start
+// depth is 0 (determineNextSupseg never picks such a front).
+struct ViewSource {
+    const float4* col;
+    const float2* dep;
+    const uint16_t* cnt;
+    size_t cnt_stride, cnt_dstride, cnt_pitch;
+    int strip_w, strip_tiles, B, b;
+    const float4* ref_col;
+    const float* ref_dep;
+};
+
+struct ViewParams {
+    ViewVdi vdi;
+    float pv_g[16];       // proj * view of the generating camera G
+    float ipv_n[16];      // inverse(proj * view) of the viewing camera N
+    int out_w, out_h;
+    int skip;             // 1: a tile whose largest count is 0 is stepped over (INSITU_OPT_VIEW_SKIP)
+    float4* out_color;    // (out_h, out_w) rgba32f accumulator
+    uint32_t* out_image;  // (out_h, out_w) packed rgba8
+};
+
+hipError_t launch_view_build(const ViewSource& src, const ViewVdi& dst, hipStream_t s);
+hipError_t launch_vdi_view(const ViewParams& p, hipStream_t s);
+
 }  // namespace insitu

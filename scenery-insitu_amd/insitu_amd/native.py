@@ -22,7 +22,7 @@ except Exception:  # pragma: no cover - torch is always present in this image
 PKG_ROOT = Path(__file__).resolve().parent.parent
 LIB_PATH = Path(os.environ.get("INSITU_HIP_LIB", PKG_ROOT / "lib" / "libinsitu_hip.so"))
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 COMM_ID_BYTES = 128
 
 MODE_PLAIN, MODE_VDI = 0, 1
@@ -32,6 +32,8 @@ BUF_VDI_COLOR, BUF_VDI_DEPTH, BUF_OCTREE, BUF_PASSES = 0, 1, 2, 3
 BUF_PLAIN_COLOR, BUF_PLAIN_DEPTH, BUF_STRIP, BUF_IMAGE = 4, 5, 6, 7
 BUF_COMPOSITED_COLOR, BUF_COMPOSITED_DEPTH, BUF_GATHERED_COLOR, BUF_GATHERED_DEPTH, BUF_COMPOSITE_PASSES = 8, 9, 10, 11, 12
 BUF_RECEIVED_COLOR, BUF_RECEIVED_DEPTH = 13, 14
+BUF_VIEW_COLOR, BUF_VIEW_IMAGE = 15, 16
+VIEW_GATHERED, VIEW_BRICK = 0, 1   # enum insitu_view_source
 
 # every symbol include/insitu_hip.h declares (tests check the .so exports all of them)
 EXPORTED_SYMBOLS = (
@@ -41,11 +43,13 @@ EXPORTED_SYMBOLS = (
     "insitu_get_stats", "insitu_pass_stats", "insitu_stream", "insitu_distribute_vdis", "insitu_gather_composited_vdis",
     "insitu_gather_composited_vdi_set", "insitu_local_group_create", "insitu_local_group_destroy",
     "insitu_set_option", "insitu_read_region", "insitu_frame_pipelined", "insitu_pipeline_flush",
+    "insitu_view_bind", "insitu_view_bind_host", "insitu_view_render",
 )
 
 # enum insitu_option
 OPT_EXACT_SEARCH, OPT_SEARCH_DEPTH, OPT_LONG_SAMPLES, OPT_ROUND_BATCH, OPT_SEARCH_OVERSUB, OPT_TILE_ORDER = range(6)
 OPT_SUPER_TILE, OPT_REGROUP, OPT_EXACT_TILE_KEYS, OPT_PIPE_TRIGGER, OPT_PIPE_OVERSUB, OPT_PIPE_SEARCH_RAYS = 8, 9, 10, 11, 12, 13
+OPT_VIEW_SKIP = 14
 
 F16 = ctypes.c_float * 16
 
@@ -80,7 +84,7 @@ class Stats(ctypes.Structure):
         ("ms_compact", ctypes.c_float), ("ms_exchange_sync", ctypes.c_float),
         ("cache_demand_bytes", ctypes.c_longlong), ("search_regroups", ctypes.c_int),
         ("ms_image_d2h", ctypes.c_float), ("ms_latency", ctypes.c_float), ("pipelined", ctypes.c_int),
-        ("ms_ingest", ctypes.c_float),
+        ("ms_ingest", ctypes.c_float), ("ms_view", ctypes.c_float),
     ]
 
 
@@ -127,6 +131,9 @@ def load() -> ctypes.CDLL:
         "insitu_read_region": (i, [vp, i, i, i, i, vp, sz]),
         "insitu_frame_pipelined": (i, [vp, ctypes.POINTER(Camera), vp, sz, ctypes.POINTER(ll)]),
         "insitu_pipeline_flush": (i, [vp, vp, sz, ctypes.POINTER(ll)]),
+        "insitu_view_bind": (i, [vp, i, i]),
+        "insitu_view_bind_host": (i, [vp, vp, vp, i, i, i, ctypes.POINTER(Camera)]),
+        "insitu_view_render": (i, [vp, ctypes.POINTER(Camera), i, i, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -249,6 +249,36 @@ class InSituContext:
                     "insitu_read_region")
         return out
 
+    # ---------------------------------------------------------------- novel views of a VDI
+    def view_bind(self, source: int = native.VIEW_BRICK, slot: int = 0):
+        """Snapshot a VDI of the last completed frame for view_render: native.VIEW_GATHERED (root of a
+        composite_vdi context) or native.VIEW_BRICK (brick `slot`'s sub-VDI); its camera is that frame's."""
+        self._check(self.lib.insitu_view_bind(self.h, int(source), int(slot)), "insitu_view_bind")
+
+    def view_bind_host(self, color: np.ndarray, depth: np.ndarray, gen_cam: scene.CameraSpec):
+        """Bind a VDI in the reference layout -- colour (W,H,S,4), depth (W,H,2S) float32, as vdi_io.read_vdi
+        returns it -- with the camera that generated it."""
+        c = np.ascontiguousarray(color, dtype=np.float32)
+        d = np.ascontiguousarray(depth, dtype=np.float32)
+        if c.ndim != 4 or c.shape[3] != 4 or d.shape != (c.shape[0], c.shape[1], 2 * c.shape[2]):
+            raise ValueError(f"view_bind_host: colour {c.shape} / depth {d.shape} are not (W,H,S,4) / (W,H,2S)")
+        cam = gen_cam.native()
+        self._check(self.lib.insitu_view_bind_host(self.h, c.ctypes.data, d.ctypes.data, c.shape[0], c.shape[1],
+                                                   c.shape[2], ctypes.byref(cam)), "insitu_view_bind_host")
+
+    def view_render(self, cam: scene.CameraSpec, out_w: int, out_h: int, want_float: bool = False):
+        """The bound VDI seen from `cam`: the (out_h, out_w, 4) rgba8 image, or with want_float the pair
+        (image, (out_h, out_w, 4) float32 accumulator)."""
+        ncam = cam.native()
+        img = np.empty((out_h, out_w, 4), np.uint8)
+        self._check(self.lib.insitu_view_render(self.h, ctypes.byref(ncam), int(out_w), int(out_h), img.ctypes.data,
+                                                img.nbytes), "insitu_view_render")
+        if not want_float:
+            return img
+        acc = np.empty((out_h, out_w, 4), np.float32)
+        self._check(self.lib.insitu_read(self.h, native.BUF_VIEW_COLOR, 0, acc.ctypes.data, acc.nbytes), "insitu_read")
+        return img, acc
+
     def stats(self) -> dict:
         st = native.Stats()
         self._check(self.lib.insitu_get_stats(self.h, ctypes.byref(st)), "insitu_get_stats")

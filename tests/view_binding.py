@@ -1,0 +1,167 @@
+"""CPU reference of novel-view VDI rendering (tests/view_ref/view_ref.c) -- TEST INFRASTRUCTURE.
+
+Builds the C99 restatement of DESIGN.md section 9 with the oracle's flags (oracle/Makefile) against
+liboracle.so, which exports the contract's pow (orc_pow), and binds it with ctypes.  Also holds what the view
+tests share: the cameras, the slab VDIs and their analytic (double precision) images.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+import subprocess
+from pathlib import Path
+
+import numpy as np
+
+import oracle_binding as orc
+from insitu_amd import scene
+
+ROOT = Path(__file__).resolve().parent.parent
+SRC = ROOT / "tests" / "view_ref" / "view_ref.c"
+LIB = ROOT / "tests" / "view_ref" / "_build" / "libview_ref.so"
+CFLAGS = ["-O3", "-march=x86-64-v3", "-std=c99", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fopenmp",
+          "-Wall", "-Wextra"]   # oracle/Makefile
+
+_lib = None
+
+
+def load():
+    global _lib
+    if _lib is not None:
+        return _lib
+    orc.load()   # builds liboracle.so when it is missing or stale
+    if not LIB.exists() or LIB.stat().st_mtime < max(SRC.stat().st_mtime, orc.LIB.stat().st_mtime):
+        LIB.parent.mkdir(parents=True, exist_ok=True)
+        # (the run path is relative to the library, so the built tree may be moved or copied)
+        subprocess.run(["gcc", *CFLAGS, "-shared", "-o", str(LIB), str(SRC), f"-L{orc.LIB.parent}", "-loracle",
+                        "-Wl,-rpath,$ORIGIN/../../../oracle/_build", "-lm"], check=True)
+    lib = ctypes.CDLL(str(LIB))
+    vp, i = ctypes.c_void_p, ctypes.c_int
+    lib.view_ref_render.argtypes = [vp, vp, i, i, i, vp, vp, i, i, i, i, vp, vp, vp]
+    _lib = lib
+    return lib
+
+
+def pv_of(cam) -> np.ndarray:
+    """proj * view as the library forms it (float, the shaders' operation order)."""
+    return orc.mat4_mul(cam.proj, cam.view)
+
+
+def render(color: np.ndarray, depth: np.ndarray, gen_cam, cam, out_w: int, out_h: int, skip: bool = True,
+           repack: bool = False, work: bool = False):
+    """The VDI (colour (W,H,S,4), depth (W,H,2S), generated from gen_cam) seen from cam:
+    (rgba8 image (out_h,out_w,4), float accumulator (out_h,out_w,4)); with work also the walk's counts over all
+    rays, (cells visited, list entries examined in them, entries blended)."""
+    lib = load()
+    c = np.ascontiguousarray(color, dtype=np.float32)
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    W, H, S = c.shape[0], c.shape[1], c.shape[2]
+    assert c.shape == (W, H, S, 4) and d.shape == (W, H, 2 * S)
+    pv_g = np.ascontiguousarray(pv_of(gen_cam), np.float32)
+    ipv_n = np.ascontiguousarray(orc.ipv_of(cam), np.float32)
+    acc = np.zeros((out_h, out_w, 4), np.float32)
+    img = np.zeros((out_h, out_w, 4), np.uint8)
+    counts = np.zeros(3, np.int64)
+    rc = lib.view_ref_render(c.ctypes.data, d.ctypes.data, W, H, S, pv_g.ctypes.data, ipv_n.ctypes.data, out_w, out_h,
+                             1 if skip else 0, 1 if repack else 0, acc.ctypes.data, img.ctypes.data, counts.ctypes.data)
+    assert rc == 0, rc
+    if work:
+        return img, acc, tuple(int(v) for v in counts)
+    return img, acc
+
+
+# ---------------------------------------------------------------- shared scenes of the view tests
+VDI_W, VDI_H, VDI_S = 64, 48, 6
+OUT_SIZES = ((64, 48), (50, 37))   # the VDI's own size; one that is neither a multiple of 8 nor that size
+
+
+def gen_camera():
+    """The generating camera of the view tests' VDIs (tests/scenes.make_scene's default orbit)."""
+    return scene.orbit_camera(VDI_W, VDI_H, yaw_deg=30.0, pitch_deg=20.0, voxel_world=1.0 / 32)
+
+
+def view_cameras() -> dict:
+    """The viewing cameras: the generating one; yaw +20, +90 (the ray crosses many columns) and +180 degrees
+    (lists walked back to front); one so close that G's frustum covers only part of the output; and one behind
+    G's eye, whose rays cross G's camera plane."""
+    W, H = VDI_W, VDI_H
+    g = dict(voxel_world=1.0 / 32)
+    yaw, pitch = math.radians(30.0), math.radians(20.0)
+    eye = 3.5 * np.array([math.cos(pitch) * math.sin(yaw), math.sin(pitch), math.cos(pitch) * math.cos(yaw)])
+    fwd = -eye / np.linalg.norm(eye)
+    side = np.cross(fwd, [0.0, 1.0, 0.0])
+    side /= np.linalg.norm(side)
+    # behind G's camera plane and to its side, looking at the volume: every ray starts behind that plane
+    # (c_w < 0 at s = 0) and crosses it
+    cross_eye = eye - 0.5 * fwd + 1.2 * side
+    cross = scene.CameraSpec(scene.look_at(cross_eye, (0.0, 0.0, 0.0)), scene.perspective(50.0, W / H), nw=1.0)
+    return {
+        "same": gen_camera(),
+        "yaw20": scene.orbit_camera(W, H, yaw_deg=50.0, pitch_deg=20.0, **g),
+        "yaw90": scene.orbit_camera(W, H, yaw_deg=120.0, pitch_deg=20.0, **g),
+        "yaw180": scene.orbit_camera(W, H, yaw_deg=210.0, pitch_deg=20.0, **g),
+        "close": scene.orbit_camera(W, H, radius=1.2, yaw_deg=75.0, pitch_deg=-10.0, fov_deg=100.0, **g),
+        "cross": cross,
+    }
+
+
+def slab_vdi(layers, W=VDI_W, H=VDI_H, S=VDI_S):
+    """A host VDI with the same supersegments in every list: layers = [(z0, z1, (r, g, b, a)), ...] in depth
+    order, z in the generating view's NDC, a = opacity per unit world length."""
+    col = np.zeros((W, H, S, 4), np.float32)
+    dep = np.zeros((W, H, 2 * S), np.float32)
+    for i, (z0, z1, rgba) in enumerate(layers):
+        col[:, :, i, :] = np.asarray(rgba, np.float32)
+        dep[:, :, 2 * i] = np.float32(z0)
+        dep[:, :, 2 * i + 1] = np.float32(z1)
+    return col, dep
+
+
+def analytic_slabs(layers, gen_cam, cam, out_w: int, out_h: int, W=VDI_W, H=VDI_H, reverse: bool = False) -> np.ndarray:
+    """Double-precision image of slab_vdi(layers) seen from cam, (out_h, out_w, 4) in [0, 1]: per layer the
+    chord of the ray inside the frustum slab -- the cells' extent X(0) <= x <= X(W), Y(0) <= y <= Y(H) and
+    z0 <= z <= z1, clipped in G's clip space -- gives alpha = 1 - (1 - a)^chord and rgb * alpha; the layers
+    blend front to back in the order the ray meets them (reverse: in the opposite order, the image a walk
+    that takes the lists the wrong way round would give).  Independent of view_ref.c: no cells, no DDA."""
+    pv_g = np.asarray(gen_cam.proj_rm, np.float64) @ np.asarray(gen_cam.view_rm, np.float64)
+    ipv_n = np.linalg.inv(np.asarray(cam.proj_rm, np.float64) @ np.asarray(cam.view_rm, np.float64))
+    x_lo, x_hi = -1.0 - 1.0 / W, 1.0 - 1.0 / W
+    y_lo, y_hi = -1.0 - 1.0 / H, 1.0 - 1.0 / H
+    out = np.zeros((out_h, out_w, 4))
+    for oy in range(out_h):
+        for ox in range(out_w):
+            uv = (ox / out_w * 2.0 - 1.0, oy / out_h * 2.0 - 1.0)
+            wf = ipv_n @ np.array([uv[0], uv[1], -1.0, 1.0])
+            wb = ipv_n @ np.array([uv[0], uv[1], 1.0, 1.0])
+            wf, wb = wf / wf[3], wb / wb[3]
+            L = float(np.linalg.norm(wb[:3] - wf[:3]))
+            cf, cb = pv_g @ wf, pv_g @ wb
+            d = cb - cf
+            segs = []
+            for z0, z1, rgba in layers:
+                lo, hi = 0.0, 1.0
+                # g(s) = g0 + s*dg >= 0 for each face of the frustum slab
+                for axis, P, sign in ((0, x_lo, 1.0), (0, x_hi, -1.0), (1, y_lo, 1.0), (1, y_hi, -1.0),
+                                      (2, float(np.float32(z0)), 1.0), (2, float(np.float32(z1)), -1.0)):
+                    g0 = sign * (cf[axis] - P * cf[3])
+                    dg = sign * (d[axis] - P * d[3])
+                    if dg > 0.0:
+                        lo = max(lo, -g0 / dg)
+                    elif dg < 0.0:
+                        hi = min(hi, -g0 / dg)
+                    elif g0 < 0.0:
+                        hi = -1.0
+                if hi > lo:
+                    segs.append((lo, (hi - lo) * L, rgba))
+            C = np.zeros(4)
+            for _, chord, rgba in sorted(segs, key=lambda t: t[0], reverse=reverse):
+                a = 1.0 - (1.0 - float(np.float32(rgba[3]))) ** chord
+                C[:3] += (1.0 - C[3]) * np.asarray(rgba[:3], np.float32).astype(np.float64) * a
+                C[3] += (1.0 - C[3]) * a
+            out[oy, ox] = C
+    return out
+
+
+def lsb_error(img: np.ndarray, analytic: np.ndarray) -> float:
+    """Largest distance of the rgba8 image from the analytic value, in units of 1/255."""
+    return float(np.max(np.abs(img.astype(np.float64) - np.clip(analytic, 0.0, 1.0) * 255.0)))

@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""Timing of the novel-view renderer (insitu_view_render) on the benchmark's scene.
+
+The scene is config 2 of bench.py on one GPU: 8 Gray-Scott bricks of 512^3 rendered at 1920x1080 with S = 20 and
+composited by the VDICompositor into a VDI of S_out = 20, gathered on the root.  That VDI is bound
+(INSITU_VIEW_GATHERED) and viewed from 36 cameras on the orbit the frame's camera lies on (10 degrees apart, the first
+one the generating camera) at 1920x1080.  Every view's kernel is timed by HIP events (insitu_stats.ms_view); after a
+warm-up pass over the orbit per setting, the passes alternate between the empty-tile skip on and off.
+
+The work of a view -- cells visited, list entries examined (24 bytes each: depth pair + colour), entries blended --
+is counted by the CPU restatement (tests/view_ref) for a few of the views (--count-views; slow), and gives the
+kernel's entry traffic in GB/s against the HBM peak.  Prints one JSON line.
+
+usage: python tools/view_bench.py [--brick 512] [--sim-n 512] [--views 36] [--passes 3] [--count-views 2]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+for _p in (ROOT / "scenery-insitu_amd", ROOT / "tests", ROOT):
+    if str(_p) not in sys.path:
+        sys.path.insert(0, str(_p))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+W_IMG, H_IMG, S = 1920, 1080, 20
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E, spec
+ENTRY_BYTES = 24        # {start, end} depth + rgba colour of one list entry
+
+
+def log(*a):
+    print(*a, file=sys.stderr, flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--brick", type=int, default=512)
+    ap.add_argument("--sim-n", type=int, default=512)
+    ap.add_argument("--views", type=int, default=36)
+    ap.add_argument("--passes", type=int, default=3, help="timed passes over the orbit per skip setting")
+    ap.add_argument("--count-views", type=int, default=2,
+                    help="views, evenly spaced on the orbit and none of them the generating one, whose work the CPU "
+                         "restatement counts")
+    ap.add_argument("--out-w", type=int, default=W_IMG)
+    ap.add_argument("--out-h", type=int, default=H_IMG)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("view_bench: needs a GPU (timings are HIP-event times of the kernel)")
+    from insitu_amd import native, scene
+    from insitu_amd.renderer import InSituContext
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n = args.brick
+    bricks = scene.grid_bricks(n * 2, 2)
+    t0 = time.perf_counter()
+    ctx = InSituContext(W_IMG, H_IMG, max_supersegments=S, bricks_per_rank=len(bricks), composite_vdi=True,
+                        max_output_supersegments=S, keep_passes=False)
+    ctx.set_transfer(scene.transfer_function(), scene.colormap_hot(), conv_scale=1.0 / 0.5, conv_offset=0.0)
+    for bid, (origin, vw, _) in enumerate(bricks):
+        v = scene.gray_scott(n, steps=1500, seed=1000 + bid, device=dev, sim_n=min(args.sim_n, n)).contiguous()
+        ctx.set_brick(bid, v, scene.brick_model(origin, vw), dtype=native.F32)
+        del v
+    vw = bricks[0][1]
+    torch.cuda.synchronize()
+    log(f"view_bench: {len(bricks)} bricks of {n}^3 in {time.perf_counter() - t0:.1f} s")
+
+    def cam_at(i):
+        return scene.orbit_camera(W_IMG, H_IMG, yaw_deg=30.0 + 360.0 / args.views * i, pitch_deg=20.0, voxel_world=vw)
+
+    gen_cam = cam_at(0)
+    ctx.frame(gen_cam)
+    ctx.view_bind(native.VIEW_GATHERED)
+    cams = [cam_at(i) for i in range(args.views)]
+    ow, oh = args.out_w, args.out_h
+
+    def orbit(skip):
+        ctx.set_option(native.OPT_VIEW_SKIP, skip)
+        ms = []
+        for cam in cams:
+            ctx.view_render(cam, ow, oh)
+            ms.append(ctx.stats()["ms_view"])
+        return ms
+
+    for skip in (1, 0):   # warm-up: every camera, both settings
+        orbit(skip)
+    times = {1: [], 0: []}
+    for _ in range(args.passes):
+        for skip in (1, 0):
+            times[skip].append(orbit(skip))
+    ctx.set_option(native.OPT_VIEW_SKIP, 1)
+    per_view = {k: np.asarray(v).min(axis=0) for k, v in times.items()}    # best of the passes, per camera
+    spread = {k: float(np.max(np.asarray(v).max(axis=0) / np.asarray(v).min(axis=0))) for k, v in times.items()}
+
+    dep = ctx.read(native.BUF_GATHERED_DEPTH)
+    counts = np.count_nonzero(dep[:, :, 0::2], axis=2)
+    tiles_empty = None
+    if W_IMG % 8 == 0 and H_IMG % 8 == 0:
+        tiles_empty = float(np.mean(counts.reshape(W_IMG // 8, 8, H_IMG // 8, 8).max(axis=(1, 3)) == 0))
+    work = []
+    if args.count_views > 0:
+        import view_binding
+        col = ctx.read(native.BUF_GATHERED_COLOR)
+        for i in (np.arange(1, args.count_views + 1) * args.views // (args.count_views + 1)).astype(int):
+            t0 = time.perf_counter()
+            rec = {"view": int(i)}
+            for skip in (1, 0):
+                _, _, (cells, examined, blended) = view_binding.render(col, dep, gen_cam, cams[i], ow, oh, skip=bool(skip),
+                                                                       work=True)
+                ms = float(per_view[skip][i])
+                rec["skip" if skip else "walk"] = {
+                    "ms": ms, "cells": cells, "entries_examined": examined, "entries_blended": blended,
+                    "entry_gb_per_s": examined * ENTRY_BYTES / (ms * 1e-3) / 1e9,
+                    "share_of_hbm_peak": examined * ENTRY_BYTES / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            work.append(rec)
+            log(f"view_bench: counted view {i} on the CPU in {time.perf_counter() - t0:.1f} s")
+    res = {
+        "metric": f"ms per novel view @{ow}x{oh} of the composited VDI {W_IMG}x{H_IMG}x{S} (8x{n}^3 volume)",
+        "views": args.views, "passes": args.passes,
+        "ms_per_view": {"skip": float(per_view[1].mean()), "walk": float(per_view[0].mean())},
+        "ms_min_max": {"skip": [float(per_view[1].min()), float(per_view[1].max())],
+                       "walk": [float(per_view[0].min()), float(per_view[0].max())]},
+        "ms_by_view_skip": [round(float(v), 4) for v in per_view[1]],
+        "ms_by_view_walk": [round(float(v), 4) for v in per_view[0]],
+        "pass_spread_max_over_min": spread,
+        "vdi": {"entries": int(counts.sum()), "nonempty_lists": int(np.count_nonzero(counts)),
+                "mean_entries_per_nonempty_list": float(counts.sum() / max(1, np.count_nonzero(counts))),
+                "empty_tile_fraction": tiles_empty},
+        "work": work,
+        "timing": "HIP events around vdi_view_kernel (insitu_stats.ms_view), best of the passes per camera",
+    }
+    ctx.close()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
