@@ -108,23 +108,42 @@ __device__ __forceinline__ int cell_of(float c, float cw, float half, int k0, in
     return (int)kf;
 }
 
+// Is the range just after ra / just before rb on the plane's >= side, as the cuts decide it: exactly when
+// clip_ge leaves lo at ra / hi at rb, and exactly when clip_lt does not.
+__device__ __forceinline__ bool above_from(const Plane& p, float ra) {
+    return (p.q > 0.0f) ? (p.t <= ra) : (p.q < 0.0f) ? (p.t > ra) : !(p.n > 0.0f);
+}
+__device__ __forceinline__ bool above_upto(const Plane& p, float rb) {
+    return (p.q > 0.0f) ? (p.t < rb) : (p.q < 0.0f) ? (p.t >= rb) : !(p.n > 0.0f);
+}
+
 struct RayG {
     f4 cf, d;
 };
 
-// 2-D DDA over granules of g cells from granule (ix, iy) to (ex, ey): every granule on the way is handed to
-// `visit` with the part of [ra, rb] inside its four planes (when not empty).  The next granule is across the
-// exit plane met first, the x plane on a tie.
+// 2-D DDA over granules of g cells inside granules [gx0, gx1] x [gy0, gy1], from the granule that owns the
+// start of [ra, rb] to the one that owns its end: every granule on the way is handed to `visit` with the part of
+// [ra, rb] inside its four planes (when not empty).  The next granule is across the exit plane met first, the x
+// plane on a tie.  (ix, iy) and (ex, ey) are where cell_of puts the two ends; the owner is that granule or, when
+// its own lower plane has the point below it or its upper plane has it above, the neighbour across that plane.
 template <class Visit>
 __device__ __forceinline__ void dda(const RayG& r, float ra, float rb, int g, int W, int H, float rw, float rh, int ix,
-                                    int iy, int ex, int ey, Visit&& visit) {
-    const int sx = ex > ix ? 1 : -1, sy = ey > iy ? 1 : -1;
+                                    int iy, int ex, int ey, int gx0, int gx1, int gy0, int gy1, Visit&& visit) {
     // the planes of granule i of an axis of n cells: its lower edge, cell i*g, and its upper edge, cell
     // min((i + 1)*g, n).  A plane is a function of its cell index alone, so a step carries the plane it
     // crosses over to the next granule instead of computing it again
     auto x_plane = [&](int i) { const int k = i * g; return plane_of(edge_of(k < W ? k : W, rw), r.cf.x, r.d.x, r.cf.w, r.d.w); };
     auto y_plane = [&](int i) { const int k = i * g; return plane_of(edge_of(k < H ? k : H, rh), r.cf.y, r.d.y, r.cf.w, r.d.w); };
     Plane xl = x_plane(ix), xh = x_plane(ix + 1), yl = y_plane(iy), yh = y_plane(iy + 1);
+    if (ix > gx0 && !above_from(xl, ra)) { ix -= 1; xh = xl; xl = x_plane(ix); }
+    else if (ix < gx1 && above_from(xh, ra)) { ix += 1; xl = xh; xh = x_plane(ix + 1); }
+    if (iy > gy0 && !above_from(yl, ra)) { iy -= 1; yh = yl; yl = y_plane(iy); }
+    else if (iy < gy1 && above_from(yh, ra)) { iy += 1; yl = yh; yh = y_plane(iy + 1); }
+    if (ex > gx0 && !above_upto(x_plane(ex), rb)) ex -= 1;
+    else if (ex < gx1 && above_upto(x_plane(ex + 1), rb)) ex += 1;
+    if (ey > gy0 && !above_upto(y_plane(ey), rb)) ey -= 1;
+    else if (ey < gy1 && above_upto(y_plane(ey + 1), rb)) ey += 1;
+    const int sx = ex > ix ? 1 : -1, sy = ey > iy ? 1 : -1;
     for (;;) {
         float lo = ra, hi = rb;
         clip_ge(xl, lo, hi);
@@ -224,11 +243,13 @@ __global__ __launch_bounds__(256) void vdi_view_kernel(const ViewParams P) {
         };
         const int kx0 = cell_x(s0, 0, W - 1), ky0 = cell_y(s0, 0, H - 1);
         const int kx1 = cell_x(s1, 0, W - 1), ky1 = cell_y(s1, 0, H - 1);
-        dda(r, s0, s1, 8, W, H, rw, rh, kx0 >> 3, ky0 >> 3, kx1 >> 3, ky1 >> 3, [&](int tx, int ty, float ta, float tb) {
+        dda(r, s0, s1, 8, W, H, rw, rh, kx0 >> 3, ky0 >> 3, kx1 >> 3, ky1 >> 3, 0, (W - 1) >> 3, 0, (H - 1) >> 3,
+            [&](int tx, int ty, float ta, float tb) {
             if (P.skip && V.tmax[ty * V.tiles_x + tx] == 0) return;
             const int xa = tx * 8, xb = xa + 7 < W - 1 ? xa + 7 : W - 1;
             const int ya = ty * 8, yb = ya + 7 < H - 1 ? ya + 7 : H - 1;
-            dda(r, ta, tb, 1, W, H, rw, rh, cell_x(ta, xa, xb), cell_y(ta, ya, yb), cell_x(tb, xa, xb), cell_y(tb, ya, yb), cell);
+            dda(r, ta, tb, 1, W, H, rw, rh, cell_x(ta, xa, xb), cell_y(ta, ya, yb), cell_x(tb, xa, xb), cell_y(tb, ya, yb),
+                xa, xb, ya, yb, cell);
         });
     }
     const size_t o = (size_t)oy * (size_t)P.out_w + (size_t)ox;

@@ -1,6 +1,8 @@
 """CPU checks of novel-view VDI rendering: the C restatement tests/view_ref/view_ref.c
 against an analytic double-precision image of slab VDIs, against the oracle's flatten from the generating camera,
-and against itself with and without the empty-tile skip and the view-layout repack.  The GPU kernel is checked
+and against itself with and without the empty-tile skip and the view-layout repack; that the walk's intervals
+partition every ray, rays lying in a cell plane included; ragged VDI sizes, S = 1 and S = 255, and host lists that
+end at a zero start depth, at S entries or at once.  The GPU kernel is checked
 against this restatement bit for bit in tests/test_gpu_view.py."""
 from __future__ import annotations
 
@@ -135,3 +137,130 @@ def test_skip_and_layout_change_no_bit(brick_vdi, name, size):
         assert np.array_equal(acc.view(np.uint32), base.view(np.uint32)), (skip, repack)
         assert np.array_equal(img, base_img)
     assert base[..., 3].sum() > 1.0
+
+
+# ---------------------------------------------------------------- every VDI size, rays in cell planes, list ends
+VDI_SIZES = ((64, 48), (50, 37), (9, 7))   # whole tiles; a ragged last tile on both axes; less than two tiles
+
+
+def _aligned_sizes(W, H):
+    """Output sizes at which, from the generating camera, whole columns or rows of rays lie in a cell plane."""
+    return ((2 * W, 2 * H), (4 * W, 4 * H), (2 * W, H), (W, 2 * H))
+
+
+@pytest.mark.parametrize("name", list(CAMS))
+@pytest.mark.parametrize("vdi_size", VDI_SIZES)
+def test_walk_partitions_the_ray(vdi_size, name):
+    """Whatever the lists hold: the intervals of the tiles a ray visits, and those of the cells it visits (skip
+    off), add up to its range [s0, s1].  Consecutive granules share the plane between them, so the sum
+    telescopes and the expected difference is 0; the allowance is one float ulp of 1 for each interval (the
+    range itself is one rounded float subtraction).  A ray left out of the walk is off by its whole range."""
+    W, H = vdi_size
+    gen, cam = vb.gen_camera(W, H), vb.view_cameras(W, H)[name]
+    col, dep = vb.slab_vdi(vb.SLAB, W, H, 1)
+    sizes = [(W, H), (50, 37), (1, 1)]
+    if name == "same":
+        sizes += [*_aligned_sizes(W, H), (130, 3)]
+    for size in sizes:
+        _, _, part = vb.render(col, dep, gen, cam, *size, skip=False, part=True)
+        span = part[..., 0]
+        assert size != (W, H) or np.count_nonzero(span) > 0   # (the camera sees the VDI)
+        for level, (cover, n) in (("tiles", (part[..., 1], part[..., 2])), ("cells", (part[..., 3], part[..., 4]))):
+            off = np.abs(cover - span)
+            print(f"partition {W}x{H} {name} {size} {level}: max |cover - span| {off.max():.3g}, "
+                  f"most intervals {int(n.max())}, rays {np.count_nonzero(span)}")
+            bad = off > n * 2.0 ** -24
+            assert not bad.any(), (size, level, int(bad.sum()), np.argwhere(bad)[:4].tolist(), float(off.max()))
+
+
+@pytest.mark.parametrize("vdi_size", VDI_SIZES[:2])
+def test_plane_aligned_rays_match_analytic(vdi_size):
+    """The generating camera at 2x and 4x the VDI's resolution: every other column and row of rays lies in a
+    cell plane (q and n at noise level there).  Only the rays in an outer plane of the extent are left out:
+    there the analytic image itself jumps."""
+    W, H = vdi_size
+    gen = vb.gen_camera(W, H)
+    col, dep = vb.slab_vdi(vb.SLAB, W, H, 1)
+    for size in _aligned_sizes(W, H):
+        img, _ = vb.render(col, dep, gen, gen, *size)
+        want = vb.analytic_slabs(vb.SLAB, gen, gen, *size, W=W, H=H)
+        out = vb.on_outer_plane(gen, gen, *size, W, H)
+        assert out.sum() <= size[0] + size[1]
+        assert np.mean(want[~out][:, 3] > 0) >= 0.9
+        err = np.abs(img.astype(np.float64) - np.clip(want, 0.0, 1.0) * 255.0).max(axis=2)
+        black = np.count_nonzero((err > LSB) & ~out & (img[..., 3] == 0))
+        print(f"aligned {W}x{H} at {size}: {err[~out].max():.3f} LSB, {int(out.sum())} rays in an outer plane left out")
+        assert err[~out].max() <= LSB, (size, int(((err > LSB) & ~out).sum()), black)
+
+
+@pytest.fixture(scope="module")
+def many_layers():
+    """20x12, S = 255: the slab cut into 255 abutting layers."""
+    col, dep = vb.layered_vdi(255, 20, 12)
+    starts = dep[:, :, 0::2]
+    assert starts.shape[2] == 255 and len(np.unique(starts[0, 0])) == 255 and np.all(starts != 0.0)
+    return col, dep
+
+
+RAGGED = [((50, 37), 3, n) for n in ("same", "yaw20", "yaw90", "yaw180", "close")] + \
+         [((9, 7), 1, n) for n in ("same", "yaw20", "yaw90", "yaw180", "close")]
+
+
+@pytest.mark.parametrize("vdi_size,S,name", RAGGED)
+def test_ragged_vdi_matches_analytic(vdi_size, S, name):
+    """VDIs whose last tile is partial on both axes (and one smaller than two tiles), S = 3 and S = 1."""
+    W, H = vdi_size
+    gen, cam = vb.gen_camera(W, H), vb.view_cameras(W, H)[name]
+    col, dep = vb.slab_vdi(vb.SLAB, W, H, S)
+    for size in ((W, H), (41, 29), (130, 3)):
+        base_img, base = vb.render(col, dep, gen, cam, *size, skip=False, repack=False)
+        want = vb.analytic_slabs(vb.SLAB, gen, cam, *size, W=W, H=H)
+        err = vb.lsb_error(base_img, want)
+        print(f"ragged {W}x{H} S={S} {name} {size}: {err:.3f} LSB, coverage {np.mean(want[..., 3] > 0):.2f}")
+        assert err <= LSB
+        for skip, repack in ((True, False), (False, True), (True, True)):
+            img, acc = vb.render(col, dep, gen, cam, *size, skip=skip, repack=repack)
+            assert np.array_equal(acc.view(np.uint32), base.view(np.uint32)), (skip, repack)
+            assert np.array_equal(img, base_img)
+    assert np.any(want[..., 3] > 0)
+
+
+@pytest.mark.parametrize("name", ["yaw20", "yaw180"])
+def test_255_layers_match_the_one_slab(many_layers, name):
+    """S at its limit (counts and the tiles' largest count are uint8): 255 abutting layers give the single
+    slab's image, first to last and last to first."""
+    col, dep = many_layers
+    W, H = 20, 12
+    gen, cam = vb.gen_camera(W, H), vb.view_cameras(W, H)[name]
+    for size in ((W, H), (41, 29)):
+        base_img, base = vb.render(col, dep, gen, cam, *size, skip=False, repack=False)
+        want = vb.analytic_slabs(vb.SLAB, gen, cam, *size, W=W, H=H)
+        err = vb.lsb_error(base_img, want)
+        print(f"255 layers {name} {size}: {err:.3f} LSB, coverage {np.mean(want[..., 3] > 0):.2f}")
+        assert np.mean(want[..., 3] > 0) > 0.2
+        assert err <= LSB
+        img, acc = vb.render(col, dep, gen, cam, *size, skip=True, repack=True)
+        assert np.array_equal(acc.view(np.uint32), base.view(np.uint32)) and np.array_equal(img, base_img)
+
+
+@pytest.mark.parametrize("repack", [False, True])
+def test_list_ends_at_first_zero_start(repack):
+    """A list ends at its first entry with start depth 0, whatever lies behind it, or at S entries."""
+    col, dep = vb.list_end_vdi()
+    W, H, S = col.shape[:3]
+    counts = np.cumprod(dep[:, :, 0::2] != 0.0, axis=2).sum(axis=2)
+    assert {0, 2, 3, S} == set(np.unique(counts))
+    assert np.count_nonzero(dep[2, 1, 0::2]) == 4 and dep[2, 1, 4] == 0.0   # 2 entries, a zero start, 2 more
+    tcol, tdep = vb.truncate_lists(col, dep)
+    assert not np.array_equal(tdep, dep) and np.array_equal(tdep[9, 3], dep[9, 3])
+    gen, cam = vb.gen_camera(W, H), vb.view_cameras(W, H)["yaw20"]
+    for size in ((W, H), (41, 29)):
+        img, acc = vb.render(col, dep, gen, cam, *size, repack=repack)
+        timg, tacc = vb.render(tcol, tdep, gen, cam, *size, repack=repack)
+        assert np.array_equal(acc.view(np.uint32), tacc.view(np.uint32)) and np.array_equal(img, timg)
+        # the entries behind the zero start would show: the same lists with that entry filled in look different
+        fcol, fdep = vb.layered_vdi(6, W, H)
+        ucol, udep = col.copy(), dep.copy()
+        ucol[2:7, 1:5, 2], udep[2:7, 1:5, 4:6] = fcol[2:7, 1:5, 2], fdep[2:7, 1:5, 4:6]
+        _, uacc = vb.render(ucol, udep, gen, cam, *size, repack=repack)
+        assert not np.array_equal(uacc, acc)

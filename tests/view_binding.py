@@ -37,7 +37,7 @@ def load():
                         "-Wl,-rpath,$ORIGIN/../../../oracle/_build", "-lm"], check=True)
     lib = ctypes.CDLL(str(LIB))
     vp, i = ctypes.c_void_p, ctypes.c_int
-    lib.view_ref_render.argtypes = [vp, vp, i, i, i, vp, vp, i, i, i, i, vp, vp, vp]
+    lib.view_ref_render.argtypes = [vp, vp, i, i, i, vp, vp, i, i, i, i, vp, vp, vp, vp]
     _lib = lib
     return lib
 
@@ -48,10 +48,13 @@ def pv_of(cam) -> np.ndarray:
 
 
 def render(color: np.ndarray, depth: np.ndarray, gen_cam, cam, out_w: int, out_h: int, skip: bool = True,
-           repack: bool = False, work: bool = False):
+           repack: bool = False, work: bool = False, part: bool = False):
     """The VDI (colour (W,H,S,4), depth (W,H,2S), generated from gen_cam) seen from cam:
     (rgba8 image (out_h,out_w,4), float accumulator (out_h,out_w,4)); with work also the walk's counts over all
-    rays, (cells visited, list entries examined in them, entries blended)."""
+    rays, (cells visited, list entries examined in them, entries blended); with part also, per output pixel,
+    (out_h, out_w, 5) doubles: the ray's range s1 - s0 inside the cells' extent (0 when clipped away), the summed
+    length and the number of the level-1 (tile) intervals it visited, and the same two of the level-2 (cell)
+    intervals -- with skip the cells of empty tiles are not among the latter."""
     lib = load()
     c = np.ascontiguousarray(color, dtype=np.float32)
     d = np.ascontiguousarray(depth, dtype=np.float32)
@@ -62,12 +65,17 @@ def render(color: np.ndarray, depth: np.ndarray, gen_cam, cam, out_w: int, out_h
     acc = np.zeros((out_h, out_w, 4), np.float32)
     img = np.zeros((out_h, out_w, 4), np.uint8)
     counts = np.zeros(3, np.int64)
+    parts = np.zeros((out_h, out_w, 5), np.float64) if part else None
     rc = lib.view_ref_render(c.ctypes.data, d.ctypes.data, W, H, S, pv_g.ctypes.data, ipv_n.ctypes.data, out_w, out_h,
-                             1 if skip else 0, 1 if repack else 0, acc.ctypes.data, img.ctypes.data, counts.ctypes.data)
+                             1 if skip else 0, 1 if repack else 0, acc.ctypes.data, img.ctypes.data, counts.ctypes.data,
+                             parts.ctypes.data if part else None)
     assert rc == 0, rc
+    res = (img, acc)
     if work:
-        return img, acc, tuple(int(v) for v in counts)
-    return img, acc
+        res += (tuple(int(v) for v in counts),)
+    if part:
+        res += (parts,)
+    return res
 
 
 # ---------------------------------------------------------------- shared scenes of the view tests
@@ -75,16 +83,15 @@ VDI_W, VDI_H, VDI_S = 64, 48, 6
 OUT_SIZES = ((64, 48), (50, 37))   # the VDI's own size; one that is neither a multiple of 8 nor that size
 
 
-def gen_camera():
+def gen_camera(W=VDI_W, H=VDI_H):
     """The generating camera of the view tests' VDIs (tests/scenes.make_scene's default orbit)."""
-    return scene.orbit_camera(VDI_W, VDI_H, yaw_deg=30.0, pitch_deg=20.0, voxel_world=1.0 / 32)
+    return scene.orbit_camera(W, H, yaw_deg=30.0, pitch_deg=20.0, voxel_world=1.0 / 32)
 
 
-def view_cameras() -> dict:
+def view_cameras(W=VDI_W, H=VDI_H) -> dict:
     """The viewing cameras: the generating one; yaw +20, +90 (the ray crosses many columns) and +180 degrees
     (lists walked back to front); one so close that G's frustum covers only part of the output; and one behind
     G's eye, whose rays cross G's camera plane."""
-    W, H = VDI_W, VDI_H
     g = dict(voxel_world=1.0 / 32)
     yaw, pitch = math.radians(30.0), math.radians(20.0)
     eye = 3.5 * np.array([math.cos(pitch) * math.sin(yaw), math.sin(pitch), math.cos(pitch) * math.cos(yaw)])
@@ -96,7 +103,7 @@ def view_cameras() -> dict:
     cross_eye = eye - 0.5 * fwd + 1.2 * side
     cross = scene.CameraSpec(scene.look_at(cross_eye, (0.0, 0.0, 0.0)), scene.perspective(50.0, W / H), nw=1.0)
     return {
-        "same": gen_camera(),
+        "same": gen_camera(W, H),
         "yaw20": scene.orbit_camera(W, H, yaw_deg=50.0, pitch_deg=20.0, **g),
         "yaw90": scene.orbit_camera(W, H, yaw_deg=120.0, pitch_deg=20.0, **g),
         "yaw180": scene.orbit_camera(W, H, yaw_deg=210.0, pitch_deg=20.0, **g),
@@ -165,3 +172,57 @@ def analytic_slabs(layers, gen_cam, cam, out_w: int, out_h: int, W=VDI_W, H=VDI_
 def lsb_error(img: np.ndarray, analytic: np.ndarray) -> float:
     """Largest distance of the rgba8 image from the analytic value, in units of 1/255."""
     return float(np.max(np.abs(img.astype(np.float64) - np.clip(analytic, 0.0, 1.0) * 255.0)))
+
+
+SLAB = [(0.9715, 0.9799, (0.5, 0.25, 0.75, 0.3))]   # about 3 to 4 world units from the generating eye
+
+
+def layered_vdi(n: int, W: int, H: int, S: int | None = None):
+    """SLAB cut into n abutting layers of its colour in every list (S slots, default n): the same analytic image
+    as the one slab, (1 - a)^chord being multiplicative over abutting chords."""
+    z0, z1, rgba = SLAB[0]
+    z = np.linspace(z0, z1, n + 1).astype(np.float32)
+    assert np.all(np.diff(z) > 0)   # the float32 depths are distinct
+    return slab_vdi([(z[i], z[i + 1], rgba) for i in range(n)], W, H, n if S is None else S)
+
+
+def list_end_vdi():
+    """A 16x8, S = 6 host VDI of lists that end in every way a host list can: most hold 3 entries and a
+    terminator; a block of them holds 2 entries, an entry with start depth 0 and 2 more entries that must not be
+    seen; a block is full, 6 entries and no terminator; a block is empty."""
+    W, H, S = 16, 8, 6
+    col, dep = layered_vdi(6, W, H)
+    col[..., 0:3] *= np.linspace(0.4, 1.0, 6, dtype=np.float32)[None, None, :, None]   # (tell the layers apart)
+    col[:, :, 3:], dep[:, :, 6:] = 0.0, 0.0
+    full_col, full_dep = layered_vdi(6, W, H)
+    col[2:7, 1:5], dep[2:7, 1:5] = full_col[2:7, 1:5], full_dep[2:7, 1:5]
+    dep[2:7, 1:5, 4], dep[2:7, 1:5, 10:] = 0.0, 0.0             # ends at entry 2; entries 3 and 4 lie behind it
+    col[9:13, 3:8], dep[9:13, 3:8] = full_col[9:13, 3:8], full_dep[9:13, 3:8]   # full, no terminator
+    col[13:16, 0:3], dep[13:16, 0:3] = 0.0, 0.0                  # empty
+    return col, dep
+
+
+def truncate_lists(col: np.ndarray, dep: np.ndarray):
+    """The VDI with everything from each list's first entry with start depth 0 on zeroed out."""
+    live = np.cumprod(dep[:, :, 0::2] != 0.0, axis=2).astype(bool)
+    return col * live[..., None], dep * np.repeat(live, 2, axis=2)
+
+
+def on_outer_plane(gen_cam, cam, out_w: int, out_h: int, W: int, H: int, tol: float = 1e-6) -> np.ndarray:
+    """(out_h, out_w) bool: the pixels whose ray, in double, has at both ends a G-NDC x or y within tol of one
+    outer plane of the cells' extent, X(0), X(W), Y(0) or Y(H) -- the ray lies in that plane, where the analytic
+    image is discontinuous."""
+    pv_g = np.asarray(gen_cam.proj_rm, np.float64) @ np.asarray(gen_cam.view_rm, np.float64)
+    ipv_n = np.linalg.inv(np.asarray(cam.proj_rm, np.float64) @ np.asarray(cam.view_rm, np.float64))
+    ox, oy = np.meshgrid(np.arange(out_w), np.arange(out_h))
+    ndc = []
+    for z in (-1.0, 1.0):
+        p = np.stack([ox / out_w * 2.0 - 1.0, oy / out_h * 2.0 - 1.0, np.full(ox.shape, z), np.ones(ox.shape)], -1)
+        p = p @ ipv_n.T
+        c = (p / p[..., 3:]) @ pv_g.T
+        ndc.append(c[..., :2] / c[..., 3:])
+    out = np.zeros(ox.shape, bool)
+    for axis, planes in ((0, (-1.0 - 1.0 / W, 1.0 - 1.0 / W)), (1, (-1.0 - 1.0 / H, 1.0 - 1.0 / H))):
+        for P in planes:
+            out |= (np.abs(ndc[0][..., axis] - P) <= tol) & (np.abs(ndc[1][..., axis] - P) <= tol)
+    return out

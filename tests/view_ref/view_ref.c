@@ -75,6 +75,14 @@ static inline int cell_of(float c, float cw, float half, int k0, int k1) {
     if (kf > (float)k1) kf = (float)k1;
     return (int)kf;
 }
+/* is the range just after ra / just before rb on the plane's >= side, as the cuts decide it: exactly when
+ * clip_ge leaves lo at ra / hi at rb, and exactly when clip_lt does not */
+static inline int above_from(plane p, float ra) {
+    return (p.q > 0.0f) ? (p.t <= ra) : (p.q < 0.0f) ? (p.t > ra) : !(p.n > 0.0f);
+}
+static inline int above_upto(plane p, float rb) {
+    return (p.q > 0.0f) ? (p.t < rb) : (p.q < 0.0f) ? (p.t >= rb) : !(p.n > 0.0f);
+}
 
 typedef struct {
     /* the lists: reference layout, or (repacked) the view layout */
@@ -89,6 +97,9 @@ typedef struct {
     int back;
     float C[4];
     long long cells, examined, blended;   /* work counters (tools/view_bench.py) */
+    /* of the pixel in hand (the partition check): summed length and number of the level-1 and level-2 intervals */
+    double cover1, cover2;
+    long long n1, n2;
 } walk;
 
 static int list_of(const walk* k, int x, int y, const float** col, const float** dep) {
@@ -145,16 +156,39 @@ static inline int cell_y(const walk* k, float s, int k0, int k1) {
     return cell_of(fmaf(s, k->d.y, k->cf.y), fmaf(s, k->d.w, k->cf.w), k->hh, k0, k1);
 }
 
-/* the 2-D DDA of section 9 over granules of g cells (8: tiles, 1: cells) */
-static void dda(walk* k, float ra, float rb, int g, int ix, int iy, int ex, int ey) {
-    const int W = k->W, H = k->H;
+/* plane i of the granules of g cells along x / y: the lower edge of cell min(i*g, n) */
+static inline plane x_plane(const walk* k, int i, int g) {
+    int c = i * g;
+    return plane_of(edge_of(c < k->W ? c : k->W, k->rw), k->cf.x, k->d.x, k->cf.w, k->d.w);
+}
+static inline plane y_plane(const walk* k, int i, int g) {
+    int c = i * g;
+    return plane_of(edge_of(c < k->H ? c : k->H, k->rh), k->cf.y, k->d.y, k->cf.w, k->d.w);
+}
+/* the granule of [i0, i1] that owns the start (end = 0) or the end (end = 1) of the range by the cuts: i, or
+ * its neighbour when i's own lower plane has the point below it or its upper plane has it above */
+static inline int own_x(const walk* k, int g, int i, int i0, int i1, float s, int end) {
+    if (i > i0) { plane p = x_plane(k, i, g); if (!(end ? above_upto(p, s) : above_from(p, s))) return i - 1; }
+    if (i < i1) { plane p = x_plane(k, i + 1, g); if (end ? above_upto(p, s) : above_from(p, s)) return i + 1; }
+    return i;
+}
+static inline int own_y(const walk* k, int g, int i, int i0, int i1, float s, int end) {
+    if (i > i0) { plane p = y_plane(k, i, g); if (!(end ? above_upto(p, s) : above_from(p, s))) return i - 1; }
+    if (i < i1) { plane p = y_plane(k, i + 1, g); if (end ? above_upto(p, s) : above_from(p, s)) return i + 1; }
+    return i;
+}
+
+/* the 2-D DDA of section 9 over granules of g cells (8: tiles, 1: cells) inside granules [gx0, gx1] x [gy0, gy1];
+ * (ix, iy) and (ex, ey) are where cell_of puts the ends of [ra, rb], corrected here to the granules that own them */
+static void dda(walk* k, float ra, float rb, int g, int ix, int iy, int ex, int ey, int gx0, int gx1, int gy0, int gy1) {
+    ix = own_x(k, g, ix, gx0, gx1, ra, 0);
+    iy = own_y(k, g, iy, gy0, gy1, ra, 0);
+    ex = own_x(k, g, ex, gx0, gx1, rb, 1);
+    ey = own_y(k, g, ey, gy0, gy1, rb, 1);
     const int sx = ex > ix ? 1 : -1, sy = ey > iy ? 1 : -1;
     for (;;) {
-        int x0 = ix * g, x1 = x0 + g, y0 = iy * g, y1 = y0 + g;
-        plane xl = plane_of(edge_of(x0, k->rw), k->cf.x, k->d.x, k->cf.w, k->d.w);
-        plane xh = plane_of(edge_of(x1 < W ? x1 : W, k->rw), k->cf.x, k->d.x, k->cf.w, k->d.w);
-        plane yl = plane_of(edge_of(y0, k->rh), k->cf.y, k->d.y, k->cf.w, k->d.w);
-        plane yh = plane_of(edge_of(y1 < H ? y1 : H, k->rh), k->cf.y, k->d.y, k->cf.w, k->d.w);
+        plane xl = x_plane(k, ix, g), xh = x_plane(k, ix + 1, g);
+        plane yl = y_plane(k, iy, g), yh = y_plane(k, iy + 1, g);
         float lo = ra, hi = rb;
         clip_ge(xl, &lo, &hi);
         clip_lt(xh, &lo, &hi);
@@ -162,11 +196,19 @@ static void dda(walk* k, float ra, float rb, int g, int ix, int iy, int ex, int 
         clip_lt(yh, &lo, &hi);
         if (hi > lo) {
             if (g == 1) {
+                k->cover2 += (double)hi - (double)lo;
+                k->n2 += 1;
                 visit_cell(k, ix, iy, lo, hi);
-            } else if (!(k->skip && k->tmax[iy * k->tiles_x + ix] == 0)) {
-                int xa = ix * 8, xb = xa + 7 < W - 1 ? xa + 7 : W - 1;
-                int ya = iy * 8, yb = ya + 7 < H - 1 ? ya + 7 : H - 1;
-                dda(k, lo, hi, 1, cell_x(k, lo, xa, xb), cell_y(k, lo, ya, yb), cell_x(k, hi, xa, xb), cell_y(k, hi, ya, yb));
+            } else {
+                k->cover1 += (double)hi - (double)lo;
+                k->n1 += 1;
+                if (!(k->skip && k->tmax[iy * k->tiles_x + ix] == 0)) {
+                    const int W = k->W, H = k->H;
+                    int xa = ix * 8, xb = xa + 7 < W - 1 ? xa + 7 : W - 1;
+                    int ya = iy * 8, yb = ya + 7 < H - 1 ? ya + 7 : H - 1;
+                    dda(k, lo, hi, 1, cell_x(k, lo, xa, xb), cell_y(k, lo, ya, yb), cell_x(k, hi, xa, xb),
+                        cell_y(k, hi, ya, yb), xa, xb, ya, yb);
+                }
             }
         }
         if (ix == ex && iy == ey) break;
@@ -176,7 +218,8 @@ static void dda(walk* k, float ra, float rb, int g, int ix, int iy, int ex, int 
     }
 }
 
-static void view_pixel(walk* k, const float* pv_g, const float* ipv_n, int ox, int oy, int out_w, int out_h) {
+/* returns s1 - s0, the part of the ray inside the cells' extent (0 when nothing is left) */
+static float view_pixel(walk* k, const float* pv_g, const float* ipv_n, int ox, int oy, int out_w, int out_h) {
     float uvx = fmaf((float)ox / (float)out_w, 2.0f, -1.0f);
     float uvy = fmaf((float)oy / (float)out_h, 2.0f, -1.0f);
     v4 front = { uvx, uvy, -1.0f, 1.0f }, backp = { uvx, uvy, 1.0f, 1.0f };
@@ -187,6 +230,8 @@ static void view_pixel(walk* k, const float* pv_g, const float* ipv_n, int ox, i
     v4 cb = mat_vec(pv_g, wb);
     k->d.x = cb.x - k->cf.x; k->d.y = cb.y - k->cf.y; k->d.z = cb.z - k->cf.z; k->d.w = cb.w - k->cf.w;
     k->C[0] = k->C[1] = k->C[2] = k->C[3] = 0.0f;
+    k->cover1 = k->cover2 = 0.0;
+    k->n1 = k->n2 = 0;
     const int W = k->W, H = k->H;
     float s0 = 0.0f, s1 = 1.0f;
     clip_ge(plane_of(edge_of(0, k->rw), k->cf.x, k->d.x, k->cf.w, k->d.w), &s0, &s1);
@@ -195,20 +240,23 @@ static void view_pixel(walk* k, const float* pv_g, const float* ipv_n, int ox, i
     clip_lt(plane_of(edge_of(H, k->rh), k->cf.y, k->d.y, k->cf.w, k->d.w), &s0, &s1);
     clip_ge(plane_of(-1.0f, k->cf.z, k->d.z, k->cf.w, k->d.w), &s0, &s1);
     clip_le(plane_of(1.0f, k->cf.z, k->d.z, k->cf.w, k->d.w), &s0, &s1);
-    if (!(s1 > s0)) return;
+    if (!(s1 > s0)) return 0.0f;
     float z0 = fmaf(s0, k->d.z, k->cf.z) / fmaf(s0, k->d.w, k->cf.w);
     float z1 = fmaf(s1, k->d.z, k->cf.z) / fmaf(s1, k->d.w, k->cf.w);
     k->back = z1 < z0;
     int kx0 = cell_x(k, s0, 0, W - 1), ky0 = cell_y(k, s0, 0, H - 1);
     int kx1 = cell_x(k, s1, 0, W - 1), ky1 = cell_y(k, s1, 0, H - 1);
-    dda(k, s0, s1, 8, kx0 >> 3, ky0 >> 3, kx1 >> 3, ky1 >> 3);
+    dda(k, s0, s1, 8, kx0 >> 3, ky0 >> 3, kx1 >> 3, ky1 >> 3, 0, (W - 1) >> 3, 0, (H - 1) >> 3);
+    return s1 - s0;
 }
 
 /* out_color: (out_h, out_w, 4) float; out_image: (out_h, out_w, 4) uint8; work (may be NULL): cells visited,
- * list entries examined in them, entries blended, over all rays.  0 on success. */
+ * list entries examined in them, entries blended, over all rays; part (may be NULL): (out_h, out_w, 5) double,
+ * per pixel s1 - s0, the summed length (each hi - lo in double) and the number of the level-1 intervals
+ * visited, and the same two of the level-2 intervals.  0 on success. */
 int view_ref_render(const float* color, const float* depth, int W, int H, int S, const float* pv_g,
                     const float* ipv_n, int out_w, int out_h, int skip, int repack, float* out_color,
-                    uint8_t* out_image, long long* work) {
+                    uint8_t* out_image, long long* work, double* part) {
     if (!color || !depth || !pv_g || !ipv_n || !out_color || !out_image) return -1;
     if (W <= 0 || H <= 0 || S <= 0 || S > 255 || out_w <= 0 || out_h <= 0) return -1;
     const int tiles_x = (W + 7) / 8, tiles_y = (H + 7) / 8;
@@ -257,8 +305,14 @@ int view_ref_render(const float* color, const float* depth, int W, int H, int S,
         k.rw = 1.0f / (float)W; k.rh = 1.0f / (float)H;
         k.hw = 0.5f * (float)W; k.hh = 0.5f * (float)H;
         for (int ox = 0; ox < out_w; ++ox) {
-            view_pixel(&k, pv_g, ipv_n, ox, oy, out_w, out_h);
+            float span = view_pixel(&k, pv_g, ipv_n, ox, oy, out_w, out_h);
             size_t o = ((size_t)oy * (size_t)out_w + (size_t)ox) * 4;
+            if (part) {
+                double* pp = part + ((size_t)oy * (size_t)out_w + (size_t)ox) * 5;
+                pp[0] = (double)span;
+                pp[1] = k.cover1; pp[2] = (double)k.n1;
+                pp[3] = k.cover2; pp[4] = (double)k.n2;
+            }
             for (int c = 0; c < 4; ++c) {
                 out_color[o + c] = k.C[c];
                 out_image[o + c] = unorm8(k.C[c]);
