@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define INSITU_ABI_VERSION 9
+#define INSITU_ABI_VERSION 10
 #define INSITU_COMM_ID_BYTES 128
 
 typedef struct insitu_ctx insitu_ctx;
@@ -81,6 +81,12 @@ enum insitu_buf {
 enum insitu_view_source {
     INSITU_VIEW_GATHERED = 0, /* root of a composite_vdi context: the gathered composited VDI (W,H,S_out) */
     INSITU_VIEW_BRICK = 1     /* brick `slot`'s sub-VDI (W,H,S)                                             */
+};
+
+/* Colour precision of a packed VDI stream (insitu_view_pack); the depths are float32 in both. */
+enum insitu_pack_format {
+    INSITU_PACK_FLOAT = 0, /* rgba32f: the bound VDI exactly, 24 bytes per stored entry                     */
+    INSITU_PACK_HALF = 1   /* rgba16f, round to nearest even (numpy's astype(float16)): 16 bytes per entry  */
 };
 
 typedef struct insitu_config {
@@ -164,6 +170,8 @@ typedef struct insitu_stats {
     float ms_ingest;             /* GPU time of the last batch of insitu_set_brick re-ingests (the bricks set
                                     between two renders; 0 until one has completed)                     */
     float ms_view;               /* GPU time of the last insitu_view_render's kernel (0 until one has run)  */
+    float ms_pack;               /* GPU time of the kernels of the last insitu_view_pack or insitu_view_bind_packed
+                                    (offsets, copy; the copies to and from the host are not in it)           */
 } insitu_stats;
 
 /* Tuning and diagnostics options (insitu_set_option); the defaults are the measured optimum. */
@@ -271,6 +279,27 @@ int insitu_view_bind_host(insitu_ctx* ctx, const void* color, const void* depth,
  * rgba32f accumulator and the image (insitu_read, insitu_buffer_bytes).  Only cam's view and projection (and its
  * inverses) are used. */
 int insitu_view_render(insitu_ctx* ctx, const insitu_camera* cam, int out_w, int out_h, void* host_out, size_t cap);
+/* ---- the packed VDI stream ----
+ * What stands in for the compacted, compressed VDI the reference publishes to a remote viewer as one message
+ * (VolumeFromFileExample.kt:907-1030: colour and depth buffers, their sizes in VDIData.bufferSizes): one
+ * self-describing byte stream of the bound VDI -- a 128-byte header (dimensions, entry count, the generating
+ * camera's proj * view), a count per pixel, then the stored entries alone, depths and colours, in pixel order.
+ * The same VDI always packs to the same bytes.  insitu_amd/vdi_io.py reads and writes the format without this
+ * library.  The three calls work on the bound VDI on the view's own stream, so they are legal while a pipelined
+ * frame is in flight, as insitu_view_render is.
+ *
+ * Bytes of the packed stream of the bound VDI in `format` (enum insitu_pack_format); 0 on error (no VDI bound,
+ * bad format).  VolumeFromFileExample.kt:907-1030 (the sizes it sends ahead of the buffers). */
+size_t insitu_view_pack_bytes(insitu_ctx* ctx, int format);
+/* Pack the bound VDI into host_out (cap >= the size above) and block.  *bytes (may be NULL) = the stream's size,
+ * also when cap is too small (then -1, and nothing is written to host_out).  VolumeFromFileExample.kt:907-1030
+ * (the compaction and compression of the VDI before it is published). */
+int insitu_view_pack(insitu_ctx* ctx, int format, void* host_out, size_t cap, size_t* bytes);
+/* Bind the VDI of a packed stream (either format; W, H and S need not be the context's), as insitu_view_bind_host
+ * does for the dense layout.  The header and `bytes` are checked on the host, the counts on the device before
+ * anything is placed by them; a rejected stream returns -1 and leaves no VDI bound.  The receiving end of
+ * VolumeFromFileExample.kt:907-1030 (the remote viewer's upload of the message). */
+int insitu_view_bind_packed(insitu_ctx* ctx, const void* data, size_t bytes);
 int insitu_get_stats(insitu_ctx* ctx, insitu_stats* out);
 /* Set a tuning option (enum insitu_option) for the following renders; -1 on an unknown option or
  * a value out of range.  Environment variables INSITU_<OPTION NAME> (INSITU_EXACT_SEARCH,

@@ -10,6 +10,7 @@
 //   gather    -> gatherCompositedVDIs' MPI_Gather (DistributedVolumes.kt:903), RCCL to rank 0
 #include "insitu_hip.h"
 #include "insitu_kernels.h"
+#include "vdi_pack_format.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -176,6 +177,17 @@ struct ViewState {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float ms = 0.0f;                    // the last render's kernel
     long long skip = 1;                 // INSITU_OPT_VIEW_SKIP
+    // the packed stream of the bound VDI (insitu_view_pack, insitu_view_bind_packed; vdi_pack.hip)
+    bool counted = false;               // pk_boff and pk_E describe the bound VDI (once per bind; view_reserve clears it)
+    unsigned long long pk_E = 0;        // its stored entries
+    uint32_t* pk_bstat = nullptr;       // PackOffsets of the bound VDI: pk_blocks blocks allocated
+    unsigned long long* pk_boff = nullptr;
+    size_t pk_blocks = 0;
+    PackTotals* pk_totals = nullptr;    // device; read back through h_totals (pinned)
+    PackTotals* h_totals = nullptr;
+    unsigned char* pk_stage = nullptr;  // the depth and colour sections on the device, kept across calls
+    size_t pk_stage_bytes = 0;
+    float ms_pack = 0.0f;               // the last pack's or unpack's kernels
 };
 
 struct insitu_ctx {
@@ -345,9 +357,11 @@ void release(insitu_ctx* c) {
     {
         ViewState& v = c->view;
         if (v.stream) (void)hipStreamSynchronize(v.stream);
-        void* vp[] = {v.vdi.col, v.vdi.dep, v.vdi.cnt, v.vdi.tmax, v.out_color, v.out_image};
+        void* vp[] = {v.vdi.col, v.vdi.dep, v.vdi.cnt, v.vdi.tmax, v.out_color, v.out_image,
+                      v.pk_bstat, v.pk_boff, v.pk_totals, v.pk_stage};
         for (void* p : vp)
             if (p) (void)hipFree(p);
+        if (v.h_totals) (void)hipHostFree(v.h_totals);
         if (v.ev0) (void)hipEventDestroy(v.ev0);
         if (v.ev1) (void)hipEventDestroy(v.ev1);
         if (v.stream) (void)hipStreamDestroy(v.stream);
@@ -1857,6 +1871,7 @@ int view_reserve(insitu_ctx* c, int W, int H, int S) {
     if (!v.ev0) HIPCHK(c, hipEventCreate(&v.ev0));
     if (!v.ev1) HIPCHK(c, hipEventCreate(&v.ev1));
     v.bound = false;
+    v.counted = false;
     const int tx = (W + 7) / 8, ty = (H + 7) / 8;
     const size_t px = (size_t)W * (size_t)H, entries = px * (size_t)S, tiles = (size_t)tx * (size_t)ty;
     int rc = 0;
@@ -1973,6 +1988,186 @@ int insitu_view_bind_host(insitu_ctx* c, const void* color, const void* depth, i
     return rc;
 }
 
+// ---- the packed stream of the bound VDI (vdi_pack.hip, vdi_pack_format.h) ----
+namespace {
+
+// the offset buffers for the bound dimensions, the totals and their pinned copy; the offset passes
+// (pack_count_kernel, pack_scan_kernel) over the view's counts on the view's stream.  Blocks; *tot = what they
+// found, *ms = their HIP-event time.
+int pack_offsets(insitu_ctx* c, int check_E, unsigned long long expect_E, PackTotals* tot, float* ms, const char* who) {
+    ViewState& v = c->view;
+    const uint64_t px = (uint64_t)v.vdi.W * (uint64_t)v.vdi.H;
+    if (px > kPackMaxPixels) return fail(c, -1, std::string(who) + ": more than 2^30 pixels");
+    const size_t blocks = (size_t)((px + (uint64_t)kPackBlockPx - 1) / (uint64_t)kPackBlockPx);
+    int rc = 0;
+    if (!v.pk_totals && (rc = dev_alloc(c, &v.pk_totals, 1))) return rc;
+    if (!v.h_totals) HIPCHK(c, hipHostMalloc((void**)&v.h_totals, sizeof(PackTotals)));
+    if (blocks > v.pk_blocks) {
+        if (v.pk_bstat) (void)hipFree(v.pk_bstat);
+        if (v.pk_boff) (void)hipFree(v.pk_boff);
+        v.pk_bstat = nullptr;
+        v.pk_boff = nullptr;
+        v.pk_blocks = 0;
+        if ((rc = dev_alloc(c, &v.pk_bstat, blocks)) || (rc = dev_alloc(c, &v.pk_boff, blocks))) return rc;
+        v.pk_blocks = blocks;
+    }
+    const PackOffsets o{v.vdi.cnt, v.pk_bstat, v.pk_boff, v.pk_totals, (uint32_t)px, (uint32_t)blocks};
+    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+    hipError_t e = launch_pack_offsets(o, v.vdi.S, check_E, expect_E, v.stream);
+    if (e != hipSuccess) return fail(c, -3, std::string(who) + ": pack_count_kernel: " + hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(v.ev1, v.stream));
+    HIPCHK(c, hipMemcpyAsync(v.h_totals, v.pk_totals, sizeof(PackTotals), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(c, hipStreamSynchronize(v.stream));
+    *tot = *v.h_totals;
+    *ms = 0.0f;
+    (void)hipEventElapsedTime(ms, v.ev0, v.ev1);
+    return 0;
+}
+
+// E and the block offsets of the bound VDI: counted once per bind
+int pack_count_bound(insitu_ctx* c, float* ms, const char* who) {
+    ViewState& v = c->view;
+    *ms = 0.0f;
+    if (v.counted) return 0;
+    PackTotals tot{};
+    if (int rc = pack_offsets(c, 0, 0, &tot, ms, who)) return rc;
+    if (tot.bad) return fail(c, -6, std::string(who) + ": a count of the bound VDI exceeds S (internal error)");
+    v.pk_E = tot.E;
+    v.counted = true;
+    return 0;
+}
+
+// room for the two sections on the device: depth at 0, colour at the next multiple of 16 (*colour_at)
+int pack_stage_reserve(insitu_ctx* c, const PackLayout& lay, size_t* colour_at) {
+    ViewState& v = c->view;
+    *colour_at = (lay.depth_bytes + 15) & ~(size_t)15;
+    const size_t need = *colour_at + lay.colour_bytes;
+    if (need > v.pk_stage_bytes) {
+        if (v.pk_stage) (void)hipFree(v.pk_stage);
+        v.pk_stage = nullptr;
+        v.pk_stage_bytes = 0;
+        if (int rc = dev_alloc(c, &v.pk_stage, need)) return rc;
+        v.pk_stage_bytes = need;
+    }
+    return 0;
+}
+
+bool pack_format_ok(int format) { return format == INSITU_PACK_FLOAT || format == INSITU_PACK_HALF; }
+
+}  // namespace
+
+size_t insitu_view_pack_bytes(insitu_ctx* c, int format) {
+    const char* err = nullptr;
+    PackLayout lay{};
+    float ms = 0.0f;
+    if (!c) err = "null context";
+    else if (!pack_format_ok(format)) err = "bad format";
+    else if (!c->view.bound) err = "no VDI bound (insitu_view_bind first)";
+    else if (hipSetDevice(c->cfg.device) != hipSuccess) err = "hipSetDevice failed";
+    else if (pack_count_bound(c, &ms, "insitu_view_pack_bytes")) return 0;   // (its message stands)
+    else if (!pack_layout((uint32_t)format, (uint32_t)c->view.vdi.W, (uint32_t)c->view.vdi.H, (uint32_t)c->view.vdi.S,
+                          c->view.pk_E, &lay)) err = "the stream's size does not fit";
+    if (err) {
+        fail(c, -1, std::string("insitu_view_pack_bytes: ") + err);
+        return 0;
+    }
+    return lay.total;
+}
+
+int insitu_view_pack(insitu_ctx* c, int format, void* host_out, size_t cap, size_t* bytes) {
+    if (!c) return fail(nullptr, -1, "insitu_view_pack: null context");
+    ViewState& v = c->view;
+    if (!pack_format_ok(format)) return fail(c, -1, "insitu_view_pack: bad format " + std::to_string(format));
+    if (!v.bound) return fail(c, -1, "insitu_view_pack: no VDI bound (insitu_view_bind first)");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    float ms_count = 0.0f;
+    if (int rc = pack_count_bound(c, &ms_count, "insitu_view_pack")) return rc;
+    PackHeader h{};
+    h.format = (uint32_t)format; h.W = (uint32_t)v.vdi.W; h.H = (uint32_t)v.vdi.H; h.S = (uint32_t)v.vdi.S;
+    h.E = v.pk_E;
+    std::memcpy(h.pv_g, v.pv_g, sizeof h.pv_g);
+    PackLayout lay{};
+    if (!pack_layout(h.format, h.W, h.H, h.S, h.E, &lay)) return fail(c, -1, "insitu_view_pack: the stream's size does not fit");
+    if (bytes) *bytes = lay.total;
+    if (!host_out || cap < lay.total)
+        return fail(c, -1, "insitu_view_pack: output buffer too small (" + std::to_string(lay.total) + " bytes needed)");
+    size_t colour_at = 0;
+    if (int rc = pack_stage_reserve(c, lay, &colour_at)) return rc;
+    PackParams p{};
+    p.vdi = v.vdi;
+    p.boff = v.pk_boff;
+    p.dep = reinterpret_cast<float2*>(v.pk_stage);
+    p.col = v.pk_stage + colour_at;
+    p.half = format == INSITU_PACK_HALF ? 1 : 0;
+    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+    hipError_t e = launch_vdi_pack(p, v.stream);
+    if (e != hipSuccess) return fail(c, -3, std::string("vdi_pack_kernel: ") + hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(v.ev1, v.stream));
+    unsigned char* out = static_cast<unsigned char*>(host_out);
+    HIPCHK(c, hipMemcpyAsync(out + kPackHeaderBytes, v.vdi.cnt, (size_t)lay.px, hipMemcpyDeviceToHost, v.stream));
+    if (h.E > 0) {
+        HIPCHK(c, hipMemcpyAsync(out + lay.depth_off, v.pk_stage, lay.depth_bytes, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(c, hipMemcpyAsync(out + lay.colour_off, v.pk_stage + colour_at, lay.colour_bytes, hipMemcpyDeviceToHost, v.stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(v.stream));
+    pack_write_header(out, h);
+    std::memset(out + kPackHeaderBytes + (size_t)lay.px, 0, lay.depth_off - kPackHeaderBytes - (size_t)lay.px);
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_pack = ms_count + ms;
+    return 0;
+}
+
+int insitu_view_bind_packed(insitu_ctx* c, const void* data, size_t bytes) {
+    if (!c) return fail(nullptr, -1, "insitu_view_bind_packed: null context");
+    ViewState& v = c->view;
+    v.bound = false;   // (a rejected stream leaves no VDI bound)
+    v.counted = false;
+    PackHeader h{};
+    PackLayout lay{};
+    if (const char* why = pack_parse(data, bytes, &h, &lay))
+        return fail(c, -1, std::string("insitu_view_bind_packed: stream rejected: ") + why);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = view_reserve(c, (int)h.W, (int)h.H, (int)h.S)) return rc;
+    size_t colour_at = 0;
+    if (int rc = pack_stage_reserve(c, lay, &colour_at)) return rc;
+    // the counts go straight into the view layout; nothing reads them as counts until they have been checked
+    const unsigned char* in = static_cast<const unsigned char*>(data);
+    HIPCHK(c, hipMemcpyAsync(v.vdi.cnt, in + kPackHeaderBytes, (size_t)lay.px, hipMemcpyHostToDevice, v.stream));
+    if (h.E > 0) {
+        HIPCHK(c, hipMemcpyAsync(v.pk_stage, in + lay.depth_off, lay.depth_bytes, hipMemcpyHostToDevice, v.stream));
+        HIPCHK(c, hipMemcpyAsync(v.pk_stage + colour_at, in + lay.colour_off, lay.colour_bytes, hipMemcpyHostToDevice, v.stream));
+    }
+    // validated on the device before anything is scattered: every count <= S, and the counts add up to E
+    PackTotals tot{};
+    float ms_count = 0.0f;
+    if (int rc = pack_offsets(c, 1, h.E, &tot, &ms_count, "insitu_view_bind_packed")) return rc;
+    if (tot.bad) {
+        if (tot.max_count > h.S)
+            return fail(c, -1, "insitu_view_bind_packed: stream rejected: a count of " + std::to_string(tot.max_count) +
+                                   " exceeds S = " + std::to_string(h.S));
+        return fail(c, -1, "insitu_view_bind_packed: stream rejected: the counts add up to " + std::to_string(tot.E) +
+                               ", the header says " + std::to_string(h.E));
+    }
+    PackParams p{};
+    p.vdi = v.vdi;
+    p.boff = v.pk_boff;
+    p.dep = reinterpret_cast<float2*>(v.pk_stage);
+    p.col = v.pk_stage + colour_at;
+    p.half = h.format == kPackHalf ? 1 : 0;
+    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+    hipError_t e = launch_vdi_unpack(p, v.stream);
+    if (e != hipSuccess) return fail(c, -3, std::string("vdi_unpack_kernel: ") + hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(v.ev1, v.stream));
+    HIPCHK(c, hipStreamSynchronize(v.stream));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_pack = ms_count + ms;
+    std::memcpy(v.pv_g, h.pv_g, sizeof v.pv_g);
+    v.pk_E = h.E;
+    v.counted = true;
+    v.bound = true;
+    return 0;
+}
+
 int insitu_view_render(insitu_ctx* c, const insitu_camera* cam, int out_w, int out_h, void* host_out, size_t cap) {
     if (!c) return fail(nullptr, -1, "insitu_view_render: null context");
     if (!cam) return fail(c, -1, "insitu_view_render: null camera");
@@ -2072,6 +2267,7 @@ int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
         out->ms_ingest = ms;
     (void)hipGetLastError();
     out->ms_view = c->view.ms;
+    out->ms_pack = c->view.ms_pack;
     out->ms_sample = out->ms_render;
     float a = 0.0f, b = 0.0f;
     if (c->mode == INSITU_MODE_VDI && f.ev_valid[EvRenderEnd] && span(EvRenderStart, EvSampleEnd, &a) &&

@@ -316,4 +316,39 @@ struct ViewParams {
 hipError_t launch_view_build(const ViewSource& src, const ViewVdi& dst, hipStream_t s);
 hipError_t launch_vdi_view(const ViewParams& p, hipStream_t s);
 
+// ---- the packed VDI stream (vdi_pack.hip, vdi_pack_format.h) ----
+constexpr int kPackBlockPx = 256;   // pixels per block of the offset passes and the copies: 4 waves x 64 pixels
+
+struct PackTotals {
+    unsigned long long E;   // the sum of the counts: the stored entries
+    uint32_t max_count;     // the largest count
+    uint32_t bad;           // 1: a count above S, or E differs from the expected one (a stream to be rejected)
+};
+
+// The offset passes over px = W*H counts: per block b of kPackBlockPx pixels bstat[b] = the sum of its counts |
+// the largest one << 24, boff[b] = the entries before its first pixel (64-bit), and the totals.
+struct PackOffsets {
+    const uint8_t* cnt;
+    uint32_t* bstat;
+    unsigned long long* boff;
+    PackTotals* totals;
+    uint32_t px, nblocks;
+};
+
+// The cooperative copy between the view layout and the stream's sections: dep = E x {start, end}, col = E x rgba
+// (float4, or 4 x binary16 when half); boff from launch_pack_offsets over vdi.cnt.
+struct PackParams {
+    ViewVdi vdi;
+    const unsigned long long* boff;
+    float2* dep;
+    void* col;
+    int half;
+};
+
+// totals->bad is set when a count exceeds S or, with check_E, when the counts do not add up to expect_E
+hipError_t launch_pack_offsets(const PackOffsets& o, int S, int check_E, unsigned long long expect_E, hipStream_t s);
+hipError_t launch_vdi_pack(const PackParams& p, hipStream_t s);     // view layout -> sections
+// sections -> view layout (vdi.cnt holds the stream's counts already, validated), then vdi.tmax from vdi.cnt
+hipError_t launch_vdi_unpack(const PackParams& p, hipStream_t s);
+
 }  // namespace insitu

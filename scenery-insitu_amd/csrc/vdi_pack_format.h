@@ -1,0 +1,138 @@
+// vdi_pack_format.h -- the packed VDI stream, format version 1: its header, the size
+// arithmetic and the binary16 conversions.  Plain C++ with no HIP in it, so that the parsing of bytes that come from
+// outside the process compiles for the CPU alone (tests/pack_format_host.cpp runs it under the sanitizers); the
+// kernels of vdi_pack.hip use the same conversions on the device.
+//
+// Stream (little-endian, as the host is): 128-byte header | W*H u8 counts, row-major (y*W + x), zero-padded to a
+// multiple of 16 | E x {start, end} float32 | E x rgba (float32, or binary16 in INSITU_PACK_HALF) -- entries pixel
+// by pixel in the counts' order, each list first entry to last; nothing follows.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#if defined(__HIPCC__)
+#define INSITU_HD __host__ __device__
+#else
+#define INSITU_HD
+#endif
+
+namespace insitu {
+
+constexpr size_t kPackHeaderBytes = 128;
+constexpr uint32_t kPackVersion = 1;
+constexpr uint32_t kPackFloat = 0, kPackHalf = 1;   // enum insitu_pack_format
+constexpr unsigned char kPackMagic[4] = {'I', 'V', 'D', 'P'};
+constexpr uint64_t kPackMaxPixels = 1ull << 30;   // (pixel indices and grid sizes stay 32-bit; entry indices are 64-bit)
+
+struct PackHeader {
+    uint32_t format, W, H, S;
+    uint64_t E;          // stored entries
+    float pv_g[16];      // proj * view of the generating camera, column-major (ViewState::pv_g)
+};
+
+// byte offsets of the sections in the stream and its size
+struct PackLayout {
+    uint64_t px;                            // W*H
+    size_t depth_off, colour_off, total;    // (the counts are at kPackHeaderBytes)
+    size_t depth_bytes, colour_bytes;
+};
+
+// The layout of a stream of these dimensions; false when a dimension is out of range, E exceeds the S slots of
+// every pixel, or a size does not fit (every product is checked: W, H and E may be anything a header can hold).
+inline bool pack_layout(uint32_t format, uint32_t W, uint32_t H, uint32_t S, uint64_t E, PackLayout* out) {
+    if (format != kPackFloat && format != kPackHalf) return false;
+    if (W == 0 || H == 0 || S < 1 || S > 255) return false;
+    const uint64_t px = (uint64_t)W * (uint64_t)H;   // (32 x 32 bits: no overflow)
+    if (px > kPackMaxPixels) return false;
+    if (E > px * (uint64_t)S) return false;          // (< 2^38)
+    const uint64_t counts = (px + 15u) & ~(uint64_t)15u;
+    const uint64_t dep = E * 8u, col = E * (format == kPackHalf ? 8u : 16u);   // (< 2^42)
+    const uint64_t total = (uint64_t)kPackHeaderBytes + counts + dep + col;
+    if (total > (uint64_t)SIZE_MAX) return false;
+    out->px = px;
+    out->depth_off = (size_t)(kPackHeaderBytes + counts);
+    out->colour_off = (size_t)(kPackHeaderBytes + counts + dep);
+    out->total = (size_t)total;
+    out->depth_bytes = (size_t)dep;
+    out->colour_bytes = (size_t)col;
+    return true;
+}
+
+inline void pack_write_header(void* out, const PackHeader& h) {
+    unsigned char b[kPackHeaderBytes] = {};
+    const uint32_t version = kPackVersion;
+    memcpy(b, kPackMagic, 4);
+    memcpy(b + 4, &version, 4);
+    memcpy(b + 8, &h.format, 4);
+    memcpy(b + 12, &h.W, 4);
+    memcpy(b + 16, &h.H, 4);
+    memcpy(b + 20, &h.S, 4);
+    memcpy(b + 24, &h.E, 8);
+    memcpy(b + 32, h.pv_g, 64);
+    memcpy(out, b, sizeof b);
+}
+
+// The header of a stream of `bytes` bytes and its layout; null when they are consistent -- magic, version, format,
+// W, H > 0, S in 1..255, `bytes` exactly the size the header implies -- else what is wrong.  Reads the first
+// kPackHeaderBytes of `data` at most.  The counts are not looked at here: whether each is <= S and they add up to
+// E is checked where they are (on the device, before anything is scattered).
+inline const char* pack_parse(const void* data, size_t bytes, PackHeader* h, PackLayout* lay) {
+    if (!data) return "null stream";
+    if (bytes < kPackHeaderBytes) return "shorter than the header";
+    const unsigned char* b = static_cast<const unsigned char*>(data);
+    if (memcmp(b, kPackMagic, 4) != 0) return "bad magic";
+    uint32_t version;
+    memcpy(&version, b + 4, 4);
+    if (version != kPackVersion) return "unknown version";
+    memcpy(&h->format, b + 8, 4);
+    memcpy(&h->W, b + 12, 4);
+    memcpy(&h->H, b + 16, 4);
+    memcpy(&h->S, b + 20, 4);
+    memcpy(&h->E, b + 24, 8);
+    memcpy(h->pv_g, b + 32, 64);
+    if (h->format != kPackFloat && h->format != kPackHalf) return "unknown format";
+    if (h->W == 0 || h->H == 0) return "W and H must be > 0";
+    if (h->S < 1 || h->S > 255) return "S must be in [1,255]";
+    if (!pack_layout(h->format, h->W, h->H, h->S, h->E, lay)) return "dimensions or entry count out of range";
+    if (lay->total != bytes) return "size differs from what the header implies";
+    return nullptr;
+}
+
+// binary32 -> binary16, round to nearest even, by integer operations (numpy's astype(float16), bit for bit:
+// subnormal halves are produced, anything that rounds beyond 65504 is infinity, a NaN keeps its top payload bits
+// and stays a NaN).  Independent of the kernel's rounding and denormal modes.  gfx950's own conversion gives the
+// same bits for every input that is not a NaN, subnormals included, but quiets the 2^23 - 2 signalling NaNs, whose
+// payload numpy keeps (all 2^32 inputs compared on an MI355X): the integer form is what makes the bytes numpy's.
+INSITU_HD inline uint16_t half_from_float_bits(uint32_t x) {
+    const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+    if (a >= 0x7f800000u) {   // inf, NaN
+        if (a == 0x7f800000u) return (uint16_t)(sign | 0x7c00u);
+        const uint32_t r = 0x7c00u | ((a & 0x007fffffu) >> 13);
+        return (uint16_t)(sign | (r == 0x7c00u ? 0x7c01u : r));
+    }
+    if (a >= 0x47800000u) return (uint16_t)(sign | 0x7c00u);   // >= 65536
+    if (a >= 0x38800000u) {   // normal halves (>= 2^-14); a carry out of the mantissa raises the exponent, up to inf
+        const uint32_t r = a - 0x38000000u;
+        return (uint16_t)(sign | ((r + 0x0fffu + ((r >> 13) & 1u)) >> 13));
+    }
+    if (a < 0x33000000u) return (uint16_t)sign;   // <= 2^-25: zero (the tie at 2^-25 goes to even)
+    const uint32_t mant = (a & 0x007fffffu) | 0x00800000u, shift = 126u - (a >> 23);   // 14..24
+    uint32_t r = mant >> shift;
+    const uint32_t rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+    if (rem > half || (rem == half && (r & 1u))) r += 1u;   // (0x3ff + 1 is the smallest normal half)
+    return (uint16_t)(sign | r);
+}
+
+// binary16 -> binary32, exact
+INSITU_HD inline uint32_t float_bits_from_half(uint16_t h) {
+    const uint32_t sign = ((uint32_t)h & 0x8000u) << 16, e = ((uint32_t)h >> 10) & 0x1fu;
+    const uint32_t m = (uint32_t)h & 0x3ffu;
+    if (e == 0x1fu) return sign | 0x7f800000u | (m << 13);
+    if (e != 0u) return sign | ((e + 112u) << 23) | (m << 13);
+    if (m == 0u) return sign;
+    const uint32_t k = (uint32_t)__builtin_clz(m) - 21u;   // subnormal, m * 2^-24: k shifts bring its top bit to 2^10
+    return sign | ((113u - k) << 23) | (((m << k) & 0x3ffu) << 13);
+}
+
+}  // namespace insitu

@@ -22,7 +22,7 @@ except Exception:  # pragma: no cover - torch is always present in this image
 PKG_ROOT = Path(__file__).resolve().parent.parent
 LIB_PATH = Path(os.environ.get("INSITU_HIP_LIB", PKG_ROOT / "lib" / "libinsitu_hip.so"))
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 COMM_ID_BYTES = 128
 
 MODE_PLAIN, MODE_VDI = 0, 1
@@ -34,6 +34,7 @@ BUF_COMPOSITED_COLOR, BUF_COMPOSITED_DEPTH, BUF_GATHERED_COLOR, BUF_GATHERED_DEP
 BUF_RECEIVED_COLOR, BUF_RECEIVED_DEPTH = 13, 14
 BUF_VIEW_COLOR, BUF_VIEW_IMAGE = 15, 16
 VIEW_GATHERED, VIEW_BRICK = 0, 1   # enum insitu_view_source
+PACK_FLOAT, PACK_HALF = 0, 1       # enum insitu_pack_format
 
 # every symbol include/insitu_hip.h declares (tests check the .so exports all of them)
 EXPORTED_SYMBOLS = (
@@ -44,6 +45,7 @@ EXPORTED_SYMBOLS = (
     "insitu_gather_composited_vdi_set", "insitu_local_group_create", "insitu_local_group_destroy",
     "insitu_set_option", "insitu_read_region", "insitu_frame_pipelined", "insitu_pipeline_flush",
     "insitu_view_bind", "insitu_view_bind_host", "insitu_view_render",
+    "insitu_view_pack_bytes", "insitu_view_pack", "insitu_view_bind_packed",
 )
 
 # enum insitu_option
@@ -84,7 +86,7 @@ class Stats(ctypes.Structure):
         ("ms_compact", ctypes.c_float), ("ms_exchange_sync", ctypes.c_float),
         ("cache_demand_bytes", ctypes.c_longlong), ("search_regroups", ctypes.c_int),
         ("ms_image_d2h", ctypes.c_float), ("ms_latency", ctypes.c_float), ("pipelined", ctypes.c_int),
-        ("ms_ingest", ctypes.c_float), ("ms_view", ctypes.c_float),
+        ("ms_ingest", ctypes.c_float), ("ms_view", ctypes.c_float), ("ms_pack", ctypes.c_float),
     ]
 
 
@@ -134,6 +136,9 @@ def load() -> ctypes.CDLL:
         "insitu_view_bind": (i, [vp, i, i]),
         "insitu_view_bind_host": (i, [vp, vp, vp, i, i, i, ctypes.POINTER(Camera)]),
         "insitu_view_render": (i, [vp, ctypes.POINTER(Camera), i, i, vp, sz]),
+        "insitu_view_pack_bytes": (sz, [vp, i]),
+        "insitu_view_pack": (i, [vp, i, vp, sz, ctypes.POINTER(sz)]),
+        "insitu_view_bind_packed": (i, [vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

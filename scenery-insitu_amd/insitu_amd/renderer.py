@@ -279,6 +279,25 @@ class InSituContext:
         self._check(self.lib.insitu_read(self.h, native.BUF_VIEW_COLOR, 0, acc.ctypes.data, acc.nbytes), "insitu_read")
         return img, acc
 
+    def view_pack(self, fmt: int = native.PACK_FLOAT) -> np.ndarray:
+        """The bound VDI as a packed stream (vdi_io.unpack_vdi reads it; view_bind_packed binds it in any
+        context): uint8, native.PACK_FLOAT exact, native.PACK_HALF with binary16 colours."""
+        n = self.lib.insitu_view_pack_bytes(self.h, int(fmt))
+        if n == 0:
+            self._check(-1, "insitu_view_pack_bytes")
+        out = np.empty(n, np.uint8)
+        got = ctypes.c_size_t(0)
+        self._check(self.lib.insitu_view_pack(self.h, int(fmt), out.ctypes.data, n, ctypes.byref(got)), "insitu_view_pack")
+        assert got.value == n
+        return out
+
+    def view_bind_packed(self, buf):
+        """Bind the VDI of a packed stream (bytes or a uint8 array; view_pack, vdi_io.pack_vdi)."""
+        b = np.ascontiguousarray(np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else buf)
+        if b.dtype != np.uint8 or b.ndim != 1:
+            raise ValueError("view_bind_packed: expected bytes or a one-dimensional uint8 array")
+        self._check(self.lib.insitu_view_bind_packed(self.h, b.ctypes.data, b.nbytes), "insitu_view_bind_packed")
+
     def stats(self) -> dict:
         st = native.Stats()
         self._check(self.lib.insitu_get_stats(self.h, ctypes.byref(st)), "insitu_get_stats")

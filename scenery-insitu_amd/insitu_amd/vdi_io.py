@@ -22,10 +22,17 @@ INTEGRATION.md shows the few Kotlin lines that turn it into a VDIDataIO file wit
 classpath.  Matrices are column-major float lists (JOML order); `projection` is the OpenGL projection
 as the reference stores it (the Vulkan fix is applied by the consumer, DistributedVolumes.kt:721),
 `projection_vulkan` the corrected one the kernels use.
+
+The packed stream (`pack_vdi` / `unpack_vdi` / `write_packed` / `read_packed`) is this
+project's own format, what stands in for the compacted VDI the reference streams to a remote viewer
+(VolumeFromFileExample.kt:907-1030): a 128-byte header, a count per pixel, and the stored entries alone.  The
+functions here are pure numpy on the reference layout, byte for byte what `InSituContext.view_pack` produces on the
+GPU, so a client without a GPU or this library's native half can read a stream.
 """
 from __future__ import annotations
 
 import json
+import struct
 from pathlib import Path
 
 import numpy as np
@@ -139,3 +146,105 @@ def write_metadata(base_path: str | Path, dataset: str, width: int, height: int,
 
 def read_metadata(path: str | Path) -> dict:
     return json.loads(Path(path).read_text())
+
+
+# ---------------------------------------------------------------- the packed stream, format version 1
+PACK_MAGIC = b"IVDP"
+PACK_VERSION = 1
+PACK_FLOAT, PACK_HALF = 0, 1          # enum insitu_pack_format
+PACK_HEADER_BYTES = 128
+PACK_MAX_PIXELS = 1 << 30
+_PACK_HEADER = struct.Struct("<4sIIIIIQ16f32x")   # magic, version, format, W, H, S, E, pv_g, zeros
+
+
+def packed_size(width: int, height: int, entries: int, fmt: int) -> int:
+    """128 + pad16(W*H) + 8 E + (16 | 8) E."""
+    return PACK_HEADER_BYTES + (width * height + 15) // 16 * 16 + entries * (8 + (8 if fmt == PACK_HALF else 16))
+
+
+def pack_vdi(colour: np.ndarray, depth: np.ndarray, pv_g, fmt: int = PACK_FLOAT) -> np.ndarray:
+    """Reference-layout VDI (colour (W, H, S, 4), depth (W, H, 2S) float32) and the generating camera's
+    proj * view (16 floats, column-major) -> the packed stream, uint8.  PACK_HALF rounds the colours to binary16
+    (astype(float16): nearest even, subnormals kept, beyond 65504 infinity); depths stay float32."""
+    colour = np.ascontiguousarray(colour, dtype=np.float32)
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if colour.ndim != 4 or colour.shape[3] != 4 or depth.shape != colour.shape[:2] + (2 * colour.shape[2],):
+        raise ValueError("expected colour (W, H, S, 4) and depth (W, H, 2S) float32")
+    W, H, S = colour.shape[:3]
+    if fmt not in (PACK_FLOAT, PACK_HALF):
+        raise ValueError(f"unknown format {fmt}")
+    if W < 1 or H < 1 or not 1 <= S <= 255 or W * H > PACK_MAX_PIXELS:
+        raise ValueError("needs W, H > 0, at most 2^30 pixels and S in [1,255]")
+    pv = np.asarray(pv_g, dtype=np.float32).reshape(-1)
+    if pv.size != 16:
+        raise ValueError("pv_g must hold 16 floats")
+    # row-major pixels (y*W + x), each list first entry to last: the boolean mask of (H, W, S) picks them in order
+    live = np.cumprod(depth[:, :, 0::2] != 0.0, axis=2).astype(bool).transpose(1, 0, 2)
+    counts = live.sum(axis=2).astype(np.uint8)
+    dep = depth.reshape(W, H, S, 2).transpose(1, 0, 2, 3)[live]
+    col = colour.transpose(1, 0, 2, 3)[live]
+    if fmt == PACK_HALF:
+        with np.errstate(over="ignore"):
+            col = col.astype(np.float16)
+    E = int(dep.shape[0])
+    out = np.zeros(packed_size(W, H, E, fmt), np.uint8)
+    out[:PACK_HEADER_BYTES] = np.frombuffer(_PACK_HEADER.pack(PACK_MAGIC, PACK_VERSION, fmt, W, H, S, E, *pv.tolist()), np.uint8)
+    out[PACK_HEADER_BYTES:PACK_HEADER_BYTES + W * H] = counts.reshape(-1)
+    d0 = PACK_HEADER_BYTES + (W * H + 15) // 16 * 16
+    out[d0:d0 + 8 * E] = np.ascontiguousarray(dep).view(np.uint8).reshape(-1)
+    out[d0 + 8 * E:] = np.ascontiguousarray(col).view(np.uint8).reshape(-1)
+    return out
+
+
+def unpack_vdi(buf) -> tuple[np.ndarray, np.ndarray, np.ndarray, int]:
+    """Packed stream -> (colour (W, H, S, 4), depth (W, H, 2S), pv_g (16,), format), float32, zero past every
+    list's count.  PACK_HALF colours are widened exactly.  ValueError on everything the library rejects: magic,
+    version, format, W or H of 0, S outside 1..255, a size that is not exactly what the header implies, a count
+    above S, counts that do not add up to the header's entry count."""
+    b = np.frombuffer(buf, np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.asarray(buf)
+    if b.dtype != np.uint8 or b.ndim != 1:
+        raise ValueError("expected bytes or a one-dimensional uint8 array")
+    if b.size < PACK_HEADER_BYTES:
+        raise ValueError("stream shorter than its header")
+    magic, version, fmt, W, H, S, E, *pv = _PACK_HEADER.unpack(b[:PACK_HEADER_BYTES].tobytes())
+    if magic != PACK_MAGIC:
+        raise ValueError("bad magic")
+    if version != PACK_VERSION:
+        raise ValueError(f"unknown version {version}")
+    if fmt not in (PACK_FLOAT, PACK_HALF):
+        raise ValueError(f"unknown format {fmt}")
+    if W == 0 or H == 0:
+        raise ValueError("W and H must be > 0")
+    if not 1 <= S <= 255:
+        raise ValueError("S must be in [1,255]")
+    if W * H > PACK_MAX_PIXELS or E > W * H * S:
+        raise ValueError("dimensions or entry count out of range")
+    if b.size != packed_size(W, H, E, fmt):
+        raise ValueError(f"stream of {b.size} bytes, the header implies {packed_size(W, H, E, fmt)}")
+    counts = b[PACK_HEADER_BYTES:PACK_HEADER_BYTES + W * H].reshape(H, W)
+    if int(counts.max()) > S:
+        raise ValueError(f"a count of {int(counts.max())} exceeds S = {S}")
+    if int(counts.sum(dtype=np.uint64)) != E:
+        raise ValueError(f"the counts add up to {int(counts.sum(dtype=np.uint64))}, the header says {E}")
+    d0 = PACK_HEADER_BYTES + (W * H + 15) // 16 * 16
+    dep = b[d0:d0 + 8 * E].view(np.float32).reshape(E, 2)
+    if fmt == PACK_HALF:
+        col = b[d0 + 8 * E:].view(np.float16).reshape(E, 4).astype(np.float32)
+    else:
+        col = b[d0 + 8 * E:].view(np.float32).reshape(E, 4)
+    live = np.arange(S)[None, None, :] < counts[:, :, None]
+    colour = np.zeros((H, W, S, 4), np.float32)
+    depth = np.zeros((H, W, S, 2), np.float32)
+    colour[live] = col
+    depth[live] = dep
+    return (np.ascontiguousarray(colour.transpose(1, 0, 2, 3)),
+            np.ascontiguousarray(depth.transpose(1, 0, 2, 3)).reshape(W, H, 2 * S), np.asarray(pv, np.float32), int(fmt))
+
+
+def write_packed(path: str | Path, colour: np.ndarray, depth: np.ndarray, pv_g, fmt: int = PACK_FLOAT) -> Path:
+    dump_to_file(pack_vdi(colour, depth, pv_g, fmt), path)
+    return Path(path)
+
+
+def read_packed(path: str | Path) -> tuple[np.ndarray, np.ndarray, np.ndarray, int]:
+    return unpack_vdi(np.fromfile(path, dtype=np.uint8))

@@ -11,7 +11,12 @@ The work of a view -- cells visited, list entries examined (24 bytes each: depth
 is counted by the CPU restatement (tests/view_ref) for a few of the views (--count-views; slow), and gives the
 kernel's entry traffic in GB/s against the HBM peak.  Prints one JSON line.
 
-usage: python tools/view_bench.py [--brick 512] [--sim-n 512] [--views 36] [--passes 3] [--count-views 2]
+--pack: after the bind, the bound VDI is packed (insitu_view_pack) in both formats and bound
+back (insitu_view_bind_packed): the stream sizes, the kernels' HIP-event time of the pack and of the unpack
+(insitu_stats.ms_pack) and the wall time of insitu_view_pack with its copy to the host, one warm-up and then the
+best of three each, go into the JSON under "pack", beside the size of the dense readback they replace.
+
+usage: python tools/view_bench.py [--brick 512] [--sim-n 512] [--views 36] [--passes 3] [--count-views 2] [--pack]
 """
 from __future__ import annotations
 
@@ -49,6 +54,7 @@ def main():
                          "restatement counts")
     ap.add_argument("--out-w", type=int, default=W_IMG)
     ap.add_argument("--out-h", type=int, default=H_IMG)
+    ap.add_argument("--pack", action="store_true", help="also time the packed stream of the bound VDI, both formats")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("view_bench: needs a GPU (timings are HIP-event times of the kernel)")
@@ -79,6 +85,30 @@ def main():
     ctx.view_bind(native.VIEW_GATHERED)
     cams = [cam_at(i) for i in range(args.views)]
     ow, oh = args.out_w, args.out_h
+
+    pack = None
+    if args.pack:
+        pack = {"dense_readback_bytes": W_IMG * H_IMG * S * 24,
+                "timing": "one warm-up, then the best of three; ms_pack: HIP events around the kernels alone"}
+        for name, fmt in (("float", native.PACK_FLOAT), ("half", native.PACK_HALF)):
+            ms_pack, ms_wall, ms_unpack, ms_bind_wall = [], [], [], []
+            for _ in range(4):
+                t0 = time.perf_counter()
+                stream = ctx.view_pack(fmt)
+                ms_wall.append((time.perf_counter() - t0) * 1e3)
+                ms_pack.append(ctx.stats()["ms_pack"])
+            for _ in range(4):
+                t0 = time.perf_counter()
+                ctx.view_bind_packed(stream)
+                ms_bind_wall.append((time.perf_counter() - t0) * 1e3)
+                ms_unpack.append(ctx.stats()["ms_pack"])
+            if fmt == native.PACK_FLOAT:   # (the round trip is exact: the same bytes again)
+                assert np.array_equal(ctx.view_pack(fmt), stream)
+            pack[name] = {"bytes": int(stream.size), "ms_pack_kernels_with_count": ms_pack[0], "ms_pack_kernels": min(ms_pack[1:]), "ms_pack_wall": min(ms_wall[1:]),
+                          "ms_unpack_kernels": min(ms_unpack[1:]), "ms_bind_packed_wall": min(ms_bind_wall[1:])}
+            del stream
+            ctx.view_bind(native.VIEW_GATHERED)   # (the orbit below views the exact VDI)
+        log(f"view_bench: pack {json.dumps(pack)}")
 
     def orbit(skip):
         ctx.set_option(native.OPT_VIEW_SKIP, skip)
@@ -133,6 +163,7 @@ def main():
                 "mean_entries_per_nonempty_list": float(counts.sum() / max(1, np.count_nonzero(counts))),
                 "empty_tile_fraction": tiles_empty},
         "work": work,
+        "pack": pack,
         "timing": "HIP events around vdi_view_kernel (insitu_stats.ms_view), best of the passes per camera",
     }
     ctx.close()
