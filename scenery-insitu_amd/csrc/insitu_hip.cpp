@@ -32,9 +32,71 @@ namespace {
 
 thread_local std::string g_create_error;
 
+int fail(insitu_ctx* c, int code, const std::string& msg);
+
+// Owner of one device allocation of `count()` elements (Pinned: of page-locked host memory), freed when it goes
+// out of scope: with the context, a frame slot, the view state or a brick, or at the end of a readback.  Reads as
+// the T* it holds.
+template <typename T, bool Pinned = false>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            std::swap(p_, o.p_);
+            std::swap(n_, o.n_);
+        }
+        return *this;
+    }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+
+    operator T*() const { return p_; }
+    T* operator->() const { return p_; }
+    T* get() const { return p_; }
+    size_t count() const { return n_; }
+
+    void reset() {
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        n_ = 0;
+    }
+    // frees what it holds, then allocates `count` elements (0: none); on failure it is left empty and the error is
+    // returned, not reported
+    hipError_t try_alloc(size_t count) {
+        reset();
+        if (count == 0) return hipSuccess;
+        const hipError_t e = Pinned ? hipHostMalloc((void**)&p_, count * sizeof(T), 0) : hipMalloc((void**)&p_, count * sizeof(T));
+        if (e != hipSuccess) {
+            p_ = nullptr;
+            (void)hipGetLastError();
+            return e;
+        }
+        n_ = count;
+        return hipSuccess;
+    }
+    // the same, reporting a failure as the context's error (code -5)
+    int alloc(insitu_ctx* c, size_t count) {
+        const hipError_t e = try_alloc(count);
+        if (e == hipSuccess) return 0;
+        return fail(c, -5, std::string(Pinned ? "hipHostMalloc of " : "hipMalloc of ") + std::to_string(count * sizeof(T)) +
+                               " bytes failed: " + hipGetErrorString(e));
+    }
+    // grow-only: keeps what it holds when that is large enough
+    int reserve(insitu_ctx* c, size_t count) { return count <= n_ ? 0 : alloc(c, count); }
+
+private:
+    T* p_ = nullptr;
+    size_t n_ = 0;
+};
+template <typename T>
+using PinnedBuf = DevBuf<T, true>;
+
 struct Brick {
-    void* d = nullptr;
-    size_t bytes = 0;
+    DevBuf<unsigned char> d;            // blocked layout with halo (insitu_sampling.h)
     int dtype = -1;
     int dims[3] = {0, 0, 0};
     float im[16];
@@ -125,31 +187,32 @@ enum FrameEvent {
 };
 
 // The generator's per-frame buffers and the frame's camera, events and stage flags.  Pipelined frames
-// (insitu_frame_pipelined) render frame k+1 into one slot while frame k is composited from the other:
-// insitu_ctx::cur points at the slot of the frame the stage functions work on, insitu_ctx::alt at the other
-// (swap_slot exchanges the pointers).  Unpipelined contexts use one slot (the other stays empty).
+// (insitu_frame_pipelined) render frame k+1 into one slot while frame k is composited from the other.  The stage
+// functions (render_frame .. gather_frame) and their helpers are handed the slot they work on and the stream(s)
+// they enqueue on; insitu_ctx::cur and ::alt only say which slot holds what (below).  Unpipelined contexts use
+// one slot (the other stays empty).
 struct FrameSlot {
-    float4* vcol_send = nullptr;
-    float2* vdep_send = nullptr;
-    uint32_t* octree = nullptr;
-    uint8_t* passes = nullptr;
-    uint16_t* seg_pending = nullptr;    // per brick and pixel: supersegments awaiting vdi_finish_kernel
-    uint16_t* seg_steps = nullptr;      // per sub-VDI entry: step count of a deferred colour
-    GenCounters* counters = nullptr;    // cache cursor + search queue counters
-    PendingRay* queue = nullptr;        // rays queued for the search kernel (B*W*H)
-    float* cache = nullptr;             // per-sample raymarch cache (32-byte chunks of 4 samples)
-    uint32_t cache_chunks = 0;
+    DevBuf<float4> vcol_send;
+    DevBuf<float2> vdep_send;
+    DevBuf<uint32_t> octree;
+    DevBuf<uint8_t> passes;
+    DevBuf<uint16_t> seg_pending;       // per brick and pixel: supersegments awaiting vdi_finish_kernel
+    DevBuf<uint16_t> seg_steps;         // per sub-VDI entry: step count of a deferred colour
+    DevBuf<GenCounters> counters;       // cache cursor + search queue counters
+    DevBuf<PendingRay> queue;           // rays queued for the search kernel (B*W*H)
+    DevBuf<float> cache;                // per-sample raymarch cache (32-byte chunks of 4 samples)
+    uint32_t cache_chunks = 0;          // its size as the kernels take it (0 while a reallocation has failed)
     // default-sized caches (insitu_ctx::cache_adaptive) grow to the measured demand: the frame's cursor (chunks
     // asked for) is copied to pinned h_ctr at the end of every render, read after the next synchronisation
     uint32_t cache_grow_to = 0;         // > cache_chunks: reallocate before the next render
     bool cache_sized = false;           // the default cache was sized from a frame's measured demand
-    GenCounters* h_ctr = nullptr;       // pinned copy of `counters` (valid after a synchronisation)
+    PinnedBuf<GenCounters> h_ctr;       // pinned copy of `counters` (valid after a synchronisation)
     bool h_ctr_pending = false;         // h_ctr's copy was enqueued and not yet observed after a synchronisation
     bool h_ctr_valid = false;           // h_ctr holds the last render's counters (observed after a synchronisation)
     bool search_launched = false;       // a render ran the persistent search kernel (fault flag valid)
-    uint32_t* tile_keys = nullptr;      // longest-tiles-first order: keys / ids (2 x B*tiles each)
-    uint32_t* tile_ids = nullptr;
-    unsigned char* sort_tmp = nullptr;  // hipcub temporary storage (insitu_ctx::sort_tmp_bytes)
+    DevBuf<uint32_t> tile_keys;         // longest-tiles-first order: keys / ids (2 x B*tiles each)
+    DevBuf<uint32_t> tile_ids;
+    DevBuf<unsigned char> sort_tmp;     // hipcub temporary storage (insitu_ctx::sort_tmp_bytes)
     float ipv[16] = {}, pv[16] = {}, view[16] = {};
     bool rendered = false, composited = false;
     bool exchanged = false;             // the compositor's input lists are complete (VDI set readable)
@@ -157,6 +220,8 @@ struct FrameSlot {
     hipStream_t search_stream = nullptr;   // pipelined: the slot's search, finish and counter copy run here
     int flag_index = 0;                    // the slot's index in insitu_ctx::slots; pipelined: its drain trigger
                                            // is insitu_ctx::pipe_flag[flag_index]
+    unsigned long long flag_value = 0;     // the last value a search of this slot stores to that flag (0: none yet);
+                                           // the slot's frames are sequential, so each stores one more than the last
     hipEvent_t ev[kFrameEvents] = {};      // (FrameEvent above)
     bool ev_valid[kFrameEvents] = {};
 };
@@ -165,13 +230,14 @@ struct FrameSlot {
 // camera -- and the output of the last insitu_view_render.  Its buffers belong to no frame slot and its work
 // runs on a stream of its own, which is idle between calls (both calls block).
 struct ViewState {
-    ViewVdi vdi{};                      // null until the first bind
-    size_t cap_entries = 0, cap_px = 0, cap_tiles = 0;   // allocated sizes (grown by a larger bind)
+    DevBuf<float4> col;                 // the snapshot's buffers (grown by a larger bind) ...
+    DevBuf<float2> dep;
+    DevBuf<uint8_t> cnt, tmax;
+    ViewVdi vdi{};                      // ... as the kernels take them, with its dimensions (view_reserve)
     float pv_g[16] = {};                // proj * view of the generating camera
     bool bound = false;
-    float4* out_color = nullptr;        // (out_h, out_w) rgba32f / rgba8 of the last render
-    uint32_t* out_image = nullptr;
-    size_t out_cap = 0;                 // pixels allocated
+    DevBuf<float4> out_color;           // (out_h, out_w) rgba32f / rgba8 of the last render (grown by a larger one)
+    DevBuf<uint32_t> out_image;
     int out_w = 0, out_h = 0;           // of the last render (0: none yet)
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -180,13 +246,11 @@ struct ViewState {
     // the packed stream of the bound VDI (insitu_view_pack, insitu_view_bind_packed; vdi_pack.hip)
     bool counted = false;               // pk_boff and pk_E describe the bound VDI (once per bind; view_reserve clears it)
     unsigned long long pk_E = 0;        // its stored entries
-    uint32_t* pk_bstat = nullptr;       // PackOffsets of the bound VDI: pk_blocks blocks allocated
-    unsigned long long* pk_boff = nullptr;
-    size_t pk_blocks = 0;
-    PackTotals* pk_totals = nullptr;    // device; read back through h_totals (pinned)
-    PackTotals* h_totals = nullptr;
-    unsigned char* pk_stage = nullptr;  // the depth and colour sections on the device, kept across calls
-    size_t pk_stage_bytes = 0;
+    DevBuf<uint32_t> pk_bstat;          // PackOffsets of the bound VDI, a block each (grown by a larger bind)
+    DevBuf<unsigned long long> pk_boff;
+    DevBuf<PackTotals> pk_totals;       // device; read back through h_totals (pinned)
+    PinnedBuf<PackTotals> h_totals;
+    DevBuf<unsigned char> pk_stage;     // the depth and colour sections on the device, kept across calls
     float ms_pack = 0.0f;               // the last pack's or unpack's kernels
 };
 
@@ -203,35 +267,34 @@ struct insitu_ctx {
     bool own_stream = false;
     ncclComm_t comm = nullptr;
     std::vector<Brick> bricks;
-    float* d_tf = nullptr;
-    float* d_cmap = nullptr;
+    DevBuf<float> d_tf;
+    DevBuf<float> d_cmap;
     int n_tf = 0, n_cm = 0;
     float cmag = 1.0f;                  // TransferDesc::cmag of the current LUTs
     float conv_scale = 1.0f, conv_offset = 0.0f;
-    float4* d_vcol_recv = nullptr;
-    float2* d_vdep_recv = nullptr;
-    uint32_t* d_pcol_send = nullptr;
-    uint32_t* d_pdep_send = nullptr;
-    uint32_t* d_pcol_recv = nullptr;
-    uint32_t* d_pdep_recv = nullptr;
-    uint32_t* d_strip = nullptr;
-    uint32_t* d_gather = nullptr;
-    uint32_t* d_image = nullptr;
-    float4* d_ref_col = nullptr;        // reference-layout staging for insitu_distribute_vdis: send | recv
-    float* d_ref_dep = nullptr;
-    uint16_t* d_ref_cnt = nullptr;      // per source strip [y][xl] counts of the host-buffer path's lists
+    DevBuf<float4> d_vcol_recv;
+    DevBuf<float2> d_vdep_recv;
+    DevBuf<uint32_t> d_pcol_send;
+    DevBuf<uint32_t> d_pdep_send;
+    DevBuf<uint32_t> d_pcol_recv;
+    DevBuf<uint32_t> d_pdep_recv;
+    DevBuf<uint32_t> d_strip;
+    DevBuf<uint32_t> d_gather;
+    DevBuf<uint32_t> d_image;
+    DevBuf<float4> d_ref_col;           // reference-layout staging for insitu_distribute_vdis: send | recv
+    DevBuf<float> d_ref_dep;
+    DevBuf<uint16_t> d_ref_cnt;         // per source strip [y][xl] counts of the host-buffer path's lists
     bool lists_from_reference = false;  // the last composite input came through insitu_distribute_vdis
     // variable-length exchange (N > 1, VDI mode): compact messages per destination
-    float4* d_ccol_send = nullptr;      // [d] regions of B*blockE entries
-    float2* d_cdep_send = nullptr;
-    uint8_t* d_meta_send = nullptr;     // [d] regions of meta_bytes
-    uint8_t* d_meta_recv = nullptr;     // [s]
-    uint32_t* d_cursor = nullptr;       // [d] entries packed for d | [N + s] entries received from s
-    uint32_t* h_tot = nullptr;          // pinned copy of d_cursor
+    DevBuf<float4> d_ccol_send;         // [d] regions of B*blockE entries
+    DevBuf<float2> d_cdep_send;
+    DevBuf<uint8_t> d_meta_send;        // [d] regions of meta_bytes
+    DevBuf<uint8_t> d_meta_recv;        // [s]
+    DevBuf<uint32_t> d_cursor;          // [d] entries packed for d | [N + s] entries received from s
+    PinnedBuf<uint32_t> h_tot;          // pinned copy of d_cursor
     size_t meta_bytes = 0;
     bool camera_set = false;
-    void* d_staging = nullptr;          // host-buffer brick uploads (kept: re-ingest every N frames)
-    size_t staging_bytes = 0;
+    DevBuf<unsigned char> d_staging;    // host-buffer brick uploads (kept: re-ingest every N frames)
     bool cache_adaptive = false;        // a default-sized sample cache: the slots' caches grow (FrameSlot)
     size_t cache_max_chunks = 0;        // growth limit (45 % of the HBM free at create, 2^32 chunks)
     int num_cus = 256;
@@ -239,7 +302,7 @@ struct insitu_ctx {
     int search_lanes = 0;               // resident lanes of the search grid for the LUT sizes below
     int search_lanes_tf = -1, search_lanes_cm = -1;
     Tuning tune;
-    unsigned long long* d_dbg = nullptr;   // INSITU_DEBUG_RAYS: per-round search timing
+    DevBuf<unsigned long long> d_dbg;      // INSITU_DEBUG_RAYS: per-round search timing
     size_t sort_tmp_bytes = 0;          // of the slots' hipcub temporary storage
     size_t dbg_entries = 0;
     std::string dbg_path;
@@ -248,26 +311,28 @@ struct insitu_ctx {
     bool composite_vdi = false;         // VDICompositor output instead of the RGBA flatten
     int S_out = 0;
     size_t cblockE = 0;                 // composited-VDI entries per strip block (S_out slots)
-    float4* d_cvdi_col = nullptr;       // this rank's composited strip (non-root ranks)
-    float2* d_cvdi_dep = nullptr;
-    float4* d_gvdi_col = nullptr;       // root: gathered composited strips [rank][block]
-    float2* d_gvdi_dep = nullptr;
+    DevBuf<float4> d_cvdi_col;          // this rank's composited strip (non-root ranks)
+    DevBuf<float2> d_cvdi_dep;
+    DevBuf<float4> d_gvdi_col;          // root: gathered composited strips [rank][block]
+    DevBuf<float2> d_gvdi_dep;
     bool gvdi_valid = false;            // root: a gather has filled them, from the frame of camera gvdi_pv
     float gvdi_pv[16] = {};
-    uint16_t* d_cvdi_cnt = nullptr;     // per pixel of this rank's composited strip: slots written (non-root ranks)
-    uint16_t* d_gvdi_cnt = nullptr;     // root: the gathered counts [rank][y][x_local]
-    uint8_t* d_cpasses = nullptr;       // compositor search passes of the strip
-    float4* d_cseq = nullptr;           // VDICompositor merge cache (kCompEntryF4 float4 per entry)
-    unsigned long long* d_cseq_cursor = nullptr;
-    unsigned long long* h_cseq_demand = nullptr;   // pinned: the last composite's demand (entries), written
+    DevBuf<uint16_t> d_cvdi_cnt;        // per pixel of this rank's composited strip: slots written (non-root ranks)
+    DevBuf<uint16_t> d_gvdi_cnt;        // root: the gathered counts [rank][y][x_local]
+    DevBuf<uint8_t> d_cpasses;          // compositor search passes of the strip
+    DevBuf<float4> d_cseq;              // VDICompositor merge cache (kCompEntryF4 float4 per entry)
+    DevBuf<unsigned long long> d_cseq_cursor;
+    PinnedBuf<unsigned long long> h_cseq_demand;   // pinned: the last composite's demand (entries), written
                                                    // by an async copy; read only by cache_observe after a sync
     bool cseq_pending = false;          // that copy is enqueued and not yet observed
     unsigned long long cseq_demand = 0; // the demand observed after the last composite's synchronisation
     unsigned long long cseq_cap = 0;    // capacity (entries)
     unsigned long long cseq_max = 0;    // growth limit (entries): 20 % of the HBM free at create
-    // the frame slots: `cur` is the one the stage functions work on.  Cross-frame pipelining
+    // the frame slots: `cur` holds the completed frame (what the unpipelined stage calls and the readers work
+    // on) and is the slot the next pipelined frame renders into.  Cross-frame pipelining
     // (insitu_frame_pipelined, DistributedVolumeRenderer.kt:530-542: the composite is one frame stale) fills
-    // the second one, `alt`, and adds the sampling and completion streams and the trigger flags below
+    // the second one, `alt` -- the frame in flight -- and adds the sampling and completion streams and the
+    // trigger flags below
     FrameSlot slots[2];
     FrameSlot* cur = &slots[0];
     FrameSlot* alt = &slots[1];
@@ -276,26 +341,19 @@ struct insitu_ctx {
     insitu_ctx& operator=(const insitu_ctx&) = delete;
     bool pipe_ready = false;            // *alt allocated, streams created
     bool pipe_inflight = false;         // *alt holds a rendered frame whose completion is pending
-    bool completing = false;            // insitu_frame_pipelined is running the stages of the frame one behind
     bool ingest_batch = false;          // re-ingests since the last render: ev_ingest0 marks their start
     hipEvent_t ev_ingest0 = nullptr, ev_ingest = nullptr;   // the last batch of re-ingests (start, end)
     hipEvent_t ev_gate = nullptr;       // pipelined: `stream`'s work so far, waited for by the next first pass
     hipStream_t pipe_sample = nullptr;  // the first pass of every pipelined frame (low priority)
     hipStream_t pipe_comp = nullptr;    // exchange, composite, gather of the frame one behind (high priority)
-    hipStream_t s_sample = nullptr;     // where insitu_render puts its first pass (null: `stream`)
     // search-drain triggers, one per slot (device memory, written at system scope): a slot's frames are
-    // sequential, so its flag only grows -- two slots' searches may overlap and drain in either order
-    unsigned long long* pipe_flag = nullptr;
-    unsigned long long pipe_seq = 0;    // frames rendered by the pipeline (the value each search stores)
+    // sequential, so its flag only grows (FrameSlot::flag_value) -- two slots' searches may overlap and drain
+    // in either order
+    DevBuf<unsigned long long> pipe_flag;
     long long pipe_frames = 0;          // frame index of the next pipelined render
     int pipe_trigger = 2;               // 0: after the previous search; 1: at its queue drain; 2: none (default:
                                         // the search keeps only the blocks its queue needs)
     bool pipe_wait_value = true;        // hipStreamWaitValue64 works here (else mode 1 falls back to 0)
-    // the trigger of the frame insitu_render is enqueuing, placed between its prepare (counters, tile keys and
-    // their sort: the slot's own buffers) and its sampling kernel, so the prepare's launches run ahead of it
-    unsigned long long* trig_flag = nullptr;         // wait for *trig_flag >= trig_value (mode 1) ...
-    unsigned long long trig_value = 0;
-    hipEvent_t trig_event = nullptr;                 // ... or for this event (mode 0)
     ViewState view;
     std::string err;
 };
@@ -322,66 +380,28 @@ int fail(insitu_ctx* c, int code, const std::string& msg) {
             return fail(ctx, -4, std::string(#expr " failed: ") + ncclGetErrorString(r_));         \
     } while (0)
 
-template <typename T>
-int dev_alloc(insitu_ctx* c, T** p, size_t count) {
-    if (count == 0) { *p = nullptr; return 0; }
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess)
-        return fail(c, -5, "hipMalloc of " + std::to_string(count * sizeof(T)) + " bytes failed: " + hipGetErrorString(e));
-    return 0;
-}
-
-// frees what alloc_slot and pipeline_setup gave a slot (any of it may be missing: a failed create); the streams
-// that use the slot are idle
-void free_slot(FrameSlot& f) {
-    void* ptrs[] = {f.vcol_send, f.vdep_send, f.octree, f.passes, f.seg_pending, f.seg_steps, f.counters, f.queue,
-                    f.cache, f.tile_keys, f.tile_ids, f.sort_tmp};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    if (f.h_ctr) (void)hipHostFree(f.h_ctr);
-    for (auto& e : f.ev)
-        if (e) (void)hipEventDestroy(e);
-    if (f.search_stream) (void)hipStreamDestroy(f.search_stream);
-}
-
+// Everything of a context that is not memory: its streams' work first, then the events, the streams, the
+// communicator and the local-group slot.  The memory (every DevBuf of the context, its slots, view and bricks) is
+// freed after it, when the caller deletes the context with the device still current.
 void release(insitu_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     // every stream first: a pipelined frame left in flight (no insitu_pipeline_flush) still runs on the sampling,
-    // search and completion streams and reads the buffers, events and trigger flags freed below (each of its
-    // waits has its producer enqueued ahead of it, so these synchronisations end)
-    for (hipStream_t st : {c->stream, c->pipe_sample, c->pipe_comp})
+    // search and completion streams and reads the buffers, events and trigger flags (each of its waits has its
+    // producer enqueued ahead of it, so these synchronisations end)
+    for (hipStream_t st : {c->stream, c->pipe_sample, c->pipe_comp, c->view.stream})
         if (st) (void)hipStreamSynchronize(st);
     for (FrameSlot& f : c->slots)
         if (f.search_stream) (void)hipStreamSynchronize(f.search_stream);
-    {
-        ViewState& v = c->view;
-        if (v.stream) (void)hipStreamSynchronize(v.stream);
-        void* vp[] = {v.vdi.col, v.vdi.dep, v.vdi.cnt, v.vdi.tmax, v.out_color, v.out_image,
-                      v.pk_bstat, v.pk_boff, v.pk_totals, v.pk_stage};
-        for (void* p : vp)
-            if (p) (void)hipFree(p);
-        if (v.h_totals) (void)hipHostFree(v.h_totals);
-        if (v.ev0) (void)hipEventDestroy(v.ev0);
-        if (v.ev1) (void)hipEventDestroy(v.ev1);
-        if (v.stream) (void)hipStreamDestroy(v.stream);
+    for (FrameSlot& f : c->slots) {
+        for (auto& e : f.ev)
+            if (e) (void)hipEventDestroy(e);
+        if (f.search_stream) (void)hipStreamDestroy(f.search_stream);
     }
-    for (auto& b : c->bricks)
-        if (b.d) (void)hipFree(b.d);
-    void* ptrs[] = {c->d_tf, c->d_cmap, c->d_vcol_recv, c->d_vdep_recv, c->d_pcol_send, c->d_pdep_send, c->d_pcol_recv, c->d_pdep_recv,
-                    c->d_strip, c->d_gather, c->d_image, c->d_cvdi_col, c->d_cvdi_dep, c->d_gvdi_col, c->d_gvdi_dep, c->d_cvdi_cnt, c->d_gvdi_cnt, c->d_cpasses, c->d_cseq, c->d_cseq_cursor, c->d_ref_col, c->d_ref_dep,
-                    c->d_dbg, c->d_ref_cnt, c->d_ccol_send, c->d_cdep_send, c->d_meta_send, c->d_meta_recv, c->d_cursor, c->d_staging};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (FrameSlot& f : c->slots) free_slot(f);
-    if (c->ev_ingest) (void)hipEventDestroy(c->ev_ingest);
-    if (c->ev_ingest0) (void)hipEventDestroy(c->ev_ingest0);
-    if (c->ev_gate) (void)hipEventDestroy(c->ev_gate);
-    if (c->pipe_flag) (void)hipFree(c->pipe_flag);
-    if (c->pipe_sample) (void)hipStreamDestroy(c->pipe_sample);
-    if (c->pipe_comp) (void)hipStreamDestroy(c->pipe_comp);
-    if (c->h_tot) (void)hipHostFree(c->h_tot);
-    if (c->h_cseq_demand) (void)hipHostFree(c->h_cseq_demand);
+    for (hipEvent_t e : {c->view.ev0, c->view.ev1, c->ev_ingest, c->ev_ingest0, c->ev_gate})
+        if (e) (void)hipEventDestroy(e);
+    for (hipStream_t st : {c->view.stream, c->pipe_sample, c->pipe_comp})
+        if (st) (void)hipStreamDestroy(st);
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->group && c->rank < (int)c->group->ranks.size() && c->group->ranks[c->rank] == c) c->group->ranks[c->rank] = nullptr;
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
@@ -392,26 +412,21 @@ bool is_root(const insitu_ctx* c) { return c->rank == 0; }
 // the other frame slot becomes the current one
 void swap_slot(insitu_ctx* c) { std::swap(c->cur, c->alt); }
 
-// the stream the current slot's readbacks run on: a pipelined frame in flight keeps `stream` busy with the
-// next frame's search, the completion stream holds nothing of it
-hipStream_t read_stream(const insitu_ctx* c) { return c->pipe_inflight ? c->pipe_comp : c->stream; }
-
-// points c->stream at `s` for a scope: the stage and readback functions enqueue on c->stream
-struct StreamScope {
-    insitu_ctx* c;
-    hipStream_t saved;
-    StreamScope(insitu_ctx* c_, hipStream_t s) : c(c_), saved(c_->stream) { c->stream = s; }
-    ~StreamScope() { c->stream = saved; }
+// the completed frame's slot and the stream its readbacks run on: with a pipelined frame in flight the completion
+// stream (the context stream may be busy with work for the next frame, the completion stream holds nothing of it)
+struct CompletedFrame {
+    FrameSlot& f;
+    hipStream_t s;
 };
+CompletedFrame completed_frame(const insitu_ctx* c) { return {*c->cur, c->pipe_inflight ? c->pipe_comp : c->stream}; }
 
-// after a stream synchronisation: the last render's cache demand (h_ctr) decides whether a
-// default-sized cache grows before the next render
-void cache_observe(insitu_ctx* c) {
-    if (c->cseq_pending) {   // the compositor merge cache's demand (insitu_composite grows it)
+// after a synchronisation of the stream of slot f's last render: its cache demand (h_ctr) decides whether a
+// default-sized cache grows before the slot's next render
+void cache_observe(insitu_ctx* c, FrameSlot& f) {
+    if (c->cseq_pending) {   // the compositor merge cache's demand (composite_frame grows it)
         c->cseq_pending = false;
         c->cseq_demand = *c->h_cseq_demand;
     }
-    FrameSlot& f = *c->cur;
     if (!f.h_ctr_pending) return;
     f.h_ctr_pending = false;
     f.h_ctr_valid = true;
@@ -421,29 +436,19 @@ void cache_observe(insitu_ctx* c) {
     if (to > f.cache_chunks) f.cache_grow_to = (uint32_t)to;
 }
 
-// (re)allocate the current slot's sample cache to `chunks` 32-byte units; on failure nothing is left allocated
-// and the error is returned
-hipError_t cache_realloc(insitu_ctx* c, size_t chunks) {
-    FrameSlot& f = *c->cur;
-    if (f.cache) (void)hipFree(f.cache);
-    f.cache = nullptr;
+// (re)allocate slot f's sample cache to `chunks` 32-byte units; on failure nothing is left allocated and the
+// error is returned
+hipError_t cache_realloc(FrameSlot& f, size_t chunks) {
     f.cache_chunks = 0;
-    hipError_t e = hipMalloc(&f.cache, chunks * 32);
-    if (e != hipSuccess) {
-        if (f.cache) (void)hipFree(f.cache);
-        f.cache = nullptr;
-        (void)hipGetLastError();
-        return e;
-    }
-    f.cache_chunks = (uint32_t)chunks;
-    return hipSuccess;
+    const hipError_t e = f.cache.try_alloc(chunks * 8);
+    if (e == hipSuccess) f.cache_chunks = (uint32_t)chunks;
+    return e;
 }
 
-// after a stream synchronisation: did a persistent kernel of the current slot's last render hit its wall-clock
-// bound?
-int check_fault(insitu_ctx* c) {
-    cache_observe(c);   // (a pending copy of the frame's counters reached h_ctr: we are after a synchronisation)
-    const FrameSlot& f = *c->cur;
+// after a synchronisation of the stream of slot f's last render: did a persistent kernel of that render hit its
+// wall-clock bound?
+int check_fault(insitu_ctx* c, FrameSlot& f) {
+    cache_observe(c, f);   // (a pending copy of the frame's counters reached h_ctr: we are after a synchronisation)
     if (!f.counters || !f.search_launched) return 0;
     uint32_t fault = 0;
     if (f.h_ctr_valid) fault = f.h_ctr->fault;
@@ -457,22 +462,21 @@ float4* cvdi_col(const insitu_ctx* c) { return c->rank == 0 ? c->d_gvdi_col : c-
 float2* cvdi_dep(const insitu_ctx* c) { return c->rank == 0 ? c->d_gvdi_dep : c->d_cvdi_dep; }
 uint16_t* cvdi_cnt(const insitu_ctx* c) { return c->rank == 0 ? c->d_gvdi_cnt : c->d_cvdi_cnt; }
 
-// records the current slot's event `i`
-void record_on(insitu_ctx* c, FrameEvent i, hipStream_t s) {
-    if (hipEventRecord(c->cur->ev[i], s) == hipSuccess) c->cur->ev_valid[i] = true;
+// records slot f's event `i` on stream s
+void record(FrameSlot& f, FrameEvent i, hipStream_t s) {
+    if (hipEventRecord(f.ev[i], s) == hipSuccess) f.ev_valid[i] = true;
 }
-void record(insitu_ctx* c, FrameEvent i) { record_on(c, i, c->stream); }
 
-// N > 1, VDI mode: pack the stored supersegments of the current slot's blocks bound for the other ranks into
-// the compact messages (vdi_compact_kernel), on `stream`, between EvCompactStart and EvCompactEnd
-hipError_t compact_enqueue(insitu_ctx* c) {
-    record(c, EvCompactStart);
-    hipError_t e = hipMemsetAsync(c->d_cursor, 0, sizeof(uint32_t) * (size_t)c->N, c->stream);
+// N > 1, VDI mode: pack the stored supersegments of slot f's blocks bound for the other ranks into the compact
+// messages (vdi_compact_kernel), on stream s, between EvCompactStart and EvCompactEnd
+hipError_t compact_enqueue(insitu_ctx* c, FrameSlot& f, hipStream_t s) {
+    record(f, EvCompactStart, s);
+    hipError_t e = hipMemsetAsync(c->d_cursor, 0, sizeof(uint32_t) * (size_t)c->N, s);
     if (e != hipSuccess) return e;
     CompactParams cp{};
-    cp.col = c->cur->vcol_send;
-    cp.dep = c->cur->vdep_send;
-    cp.pend = c->cur->seg_pending;
+    cp.col = f.vcol_send;
+    cp.dep = f.vdep_send;
+    cp.pend = f.seg_pending;
     cp.pend_stride = (size_t)c->W * (size_t)c->H;
     cp.W = c->W; cp.H = c->H; cp.S = c->S; cp.B = c->BV; cp.nstrips = c->N; cp.strip_w = c->strip_w;
     cp.strip_tiles = c->strip_tiles; cp.ytiles = (c->H + 7) / 8; cp.skip_d = c->rank;
@@ -482,18 +486,18 @@ hipError_t compact_enqueue(insitu_ctx* c) {
     cp.out_meta = c->d_meta_send;
     cp.meta_bytes = c->meta_bytes;
     cp.cursor = c->d_cursor;
-    e = launch_vdi_compact(cp, c->stream);
-    if (e == hipSuccess) record(c, EvCompactEnd);
+    e = launch_vdi_compact(cp, s);
+    if (e == hipSuccess) record(f, EvCompactEnd, s);
     return e;
 }
 
 // local group: before this rank rewrites buffers its peers copy from (send blocks, counts, strips),
-// order its stream after the peers' last reads of them (write-after-read across streams)
-hipError_t wait_peer_reads(insitu_ctx* c) {
+// order stream s after the peers' last reads of them (write-after-read across streams)
+hipError_t wait_peer_reads(insitu_ctx* c, hipStream_t s) {
     if (!c->group) return hipSuccess;
     for (const insitu_ctx* q : c->group->ranks) {
         if (!q || q == c || !q->cur->ev_valid[EvPeerReadsDone]) continue;
-        hipError_t e = hipStreamWaitEvent(c->stream, q->cur->ev[EvPeerReadsDone], 0);
+        hipError_t e = hipStreamWaitEvent(s, q->cur->ev[EvPeerReadsDone], 0);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -514,24 +518,23 @@ int alloc_slot(insitu_ctx* c, FrameSlot& f, size_t chunks) {
     if ((rc = create_slot_events(c, f))) return rc;
     const size_t sendE = (size_t)c->N * (size_t)c->BV * c->blockE;
     const size_t px = (size_t)c->BV * (size_t)c->W * (size_t)c->H;
-    if ((rc = dev_alloc(c, &f.vcol_send, sendE)) || (rc = dev_alloc(c, &f.vdep_send, sendE))) return rc;
+    if ((rc = f.vcol_send.alloc(c, sendE)) || (rc = f.vdep_send.alloc(c, sendE))) return rc;
     const size_t oct = (size_t)c->BV * (size_t)c->S * (size_t)c->ncx * (size_t)c->ncy;
-    if ((rc = dev_alloc(c, &f.octree, oct ? oct : 1))) return rc;
-    if ((rc = dev_alloc(c, &f.seg_pending, px)) || (rc = dev_alloc(c, &f.seg_steps, sendE))) return rc;
+    if ((rc = f.octree.alloc(c, oct ? oct : 1))) return rc;
+    if ((rc = f.seg_pending.alloc(c, px)) || (rc = f.seg_steps.alloc(c, sendE))) return rc;
     // per-pixel supersegment counts: empty until the first render (the slots are not zero-filled)
     if (hipMemset(f.seg_pending, 0, sizeof(uint16_t) * px) != hipSuccess)
         return fail(c, -3, "hipMemset of the supersegment counts failed");
-    if (c->cfg.keep_passes && (rc = dev_alloc(c, &f.passes, px))) return rc;
+    if (c->cfg.keep_passes && (rc = f.passes.alloc(c, px))) return rc;
     // generator counters, zeroed here so the fault flag reads 0 before any render (the host-buffer path
     // never renders)
-    if ((rc = dev_alloc(c, &f.counters, 1))) return rc;
+    if ((rc = f.counters.alloc(c, 1))) return rc;
     if (hipMemset(f.counters, 0, sizeof(GenCounters)) != hipSuccess)
         return fail(c, -3, "hipMemset of the generator counters failed");
     if (chunks == 0) return 0;
-    if ((rc = dev_alloc(c, &f.cache, chunks * 8)) || (rc = dev_alloc(c, &f.queue, (size_t)c->B * (size_t)c->W * (size_t)c->H)))
+    if ((rc = f.cache.alloc(c, chunks * 8)) || (rc = f.queue.alloc(c, (size_t)c->B * (size_t)c->W * (size_t)c->H)))
         return rc;
-    if (hipHostMalloc((void**)&f.h_ctr, sizeof(GenCounters), 0) != hipSuccess)
-        return fail(c, -5, "hipHostMalloc of the generator counters failed");
+    if (f.h_ctr.try_alloc(1) != hipSuccess) return fail(c, -5, "hipHostMalloc of the generator counters failed");
     std::memset(f.h_ctr, 0, sizeof(GenCounters));
     f.cache_chunks = (uint32_t)chunks;
     // longest-tiles-first order of the sampling kernel: keys, ids and the sort's scratch (the key keeps 24
@@ -542,8 +545,8 @@ int alloc_slot(insitu_ctx* c, FrameSlot& f, size_t chunks) {
         size_t tb = 0;
         if (sort_tiles_desc(nullptr, tb, nullptr, nullptr, nullptr, nullptr, (int)ntile, nullptr) != hipSuccess)
             return fail(c, -3, "hipcub radix sort: temporary storage query failed");
-        if ((rc = dev_alloc(c, &f.tile_keys, 2 * ntile)) || (rc = dev_alloc(c, &f.tile_ids, 2 * ntile)) ||
-            (rc = dev_alloc(c, &f.sort_tmp, tb + 1)))
+        if ((rc = f.tile_keys.alloc(c, 2 * ntile)) || (rc = f.tile_ids.alloc(c, 2 * ntile)) ||
+            (rc = f.sort_tmp.alloc(c, tb + 1)))
             return rc;
         c->sort_tmp_bytes = tb;
     }
@@ -659,18 +662,18 @@ int insitu_create(const insitu_config* cfg, insitu_ctx** out) {
         if (c->N > 1) {
             // compact exchange: send regions per destination, receive regions per source, meta blocks
             c->meta_bytes = compact_meta_bytes(c->BV, c->strip_tiles, (c->H + 7) / 8);
-            if ((rc = dev_alloc(c, &c->d_vcol_recv, sendE)) || (rc = dev_alloc(c, &c->d_vdep_recv, sendE)) ||
-                (rc = dev_alloc(c, &c->d_ccol_send, sendE)) || (rc = dev_alloc(c, &c->d_cdep_send, sendE)) ||
-                (rc = dev_alloc(c, &c->d_meta_send, (size_t)c->N * c->meta_bytes)) ||
-                (rc = dev_alloc(c, &c->d_meta_recv, (size_t)c->N * c->meta_bytes)) ||
-                (rc = dev_alloc(c, &c->d_cursor, 2 * (size_t)c->N)))
+            if ((rc = c->d_vcol_recv.alloc(c, sendE)) || (rc = c->d_vdep_recv.alloc(c, sendE)) ||
+                (rc = c->d_ccol_send.alloc(c, sendE)) || (rc = c->d_cdep_send.alloc(c, sendE)) ||
+                (rc = c->d_meta_send.alloc(c, (size_t)c->N * c->meta_bytes)) ||
+                (rc = c->d_meta_recv.alloc(c, (size_t)c->N * c->meta_bytes)) ||
+                (rc = c->d_cursor.alloc(c, 2 * (size_t)c->N)))
                 return bail(rc);
             // received counts/offsets read as empty lists until the first exchange fills them
             if (hipMemset(c->d_meta_recv, 0, (size_t)c->N * c->meta_bytes) != hipSuccess) {
                 c->err = "hipMemset of the exchange meta blocks failed";
                 return bail(-3);
             }
-            if (hipHostMalloc((void**)&c->h_tot, 2 * sizeof(uint32_t) * (size_t)c->N, 0) != hipSuccess) {
+            if (c->h_tot.try_alloc(2 * (size_t)c->N) != hipSuccess) {
                 c->err = "hipHostMalloc of the exchange totals failed";
                 return bail(-5);
             }
@@ -709,22 +712,22 @@ int insitu_create(const insitu_config* cfg, insitu_ctx** out) {
         if (const char* dbg = std::getenv("INSITU_DEBUG_RAYS")) {   // diagnostics (tools/ray_timing.py)
             if (c->slots[0].queue) {
                 c->dbg_entries = (size_t)c->BV * (size_t)c->W * (size_t)c->H;
-                if ((rc = dev_alloc(c, &c->d_dbg, c->dbg_entries * 4))) return bail(rc);
+                if ((rc = c->d_dbg.alloc(c, c->dbg_entries * 4))) return bail(rc);
                 c->dbg_path = dbg;
             }
         }
         if (is_root(c)) {
-            if ((rc = dev_alloc(c, &c->d_gather, (size_t)c->N * c->stripPx)) ||
-                (rc = dev_alloc(c, &c->d_image, (size_t)c->W * (size_t)c->H)))
+            if ((rc = c->d_gather.alloc(c, (size_t)c->N * c->stripPx)) ||
+                (rc = c->d_image.alloc(c, (size_t)c->W * (size_t)c->H)))
                 return bail(rc);
-        } else if ((rc = dev_alloc(c, &c->d_strip, c->stripPx))) {
+        } else if ((rc = c->d_strip.alloc(c, c->stripPx))) {
             return bail(rc);
         }
         if (k.composite_vdi) {
             c->composite_vdi = true;
             c->S_out = k.max_output_supersegments > 0 ? k.max_output_supersegments : c->S;
             c->cblockE = (size_t)c->strip_tiles * (size_t)c->S_out * (size_t)c->H * 8;
-            if ((rc = dev_alloc(c, &c->d_cpasses, c->stripPx))) return bail(rc);
+            if ((rc = c->d_cpasses.alloc(c, c->stripPx))) return bail(rc);
             // merge cache of the compositor: an eighth of the V*S entries per pixel to start with, grown to
             // a composite's demand when it did not fit (the waves that found no room merge every pass)
             // growth budget: 20 % of the HBM free at create (the simulation and the sample cache share the GPU)
@@ -733,20 +736,20 @@ int insitu_create(const insitu_config* cfg, insitu_ctx** out) {
             c->cseq_max = std::max<unsigned long long>(64ull * 64ull, (unsigned long long)(freeb / 5 / (16 * kCompEntryF4)));
             c->cseq_cap = std::min(c->cseq_max, std::max<unsigned long long>(
                 64ull * 64ull, (unsigned long long)c->V * c->stripPx * (unsigned long long)c->S / 8));
-            if ((rc = dev_alloc(c, &c->d_cseq, (size_t)kCompEntryF4 * (size_t)c->cseq_cap)) || (rc = dev_alloc(c, &c->d_cseq_cursor, 1)))
+            if ((rc = c->d_cseq.alloc(c, (size_t)kCompEntryF4 * (size_t)c->cseq_cap)) || (rc = c->d_cseq_cursor.alloc(c, 1)))
                 return bail(rc);
-            if (hipHostMalloc((void**)&c->h_cseq_demand, sizeof(unsigned long long), 0) != hipSuccess) {
+            if (c->h_cseq_demand.try_alloc(1) != hipSuccess) {
                 c->err = "hipHostMalloc of the compositor demand failed";
                 return bail(-5);
             }
             *c->h_cseq_demand = 0;
             if (is_root(c)) {
-                if ((rc = dev_alloc(c, &c->d_gvdi_col, (size_t)c->N * c->cblockE)) ||
-                    (rc = dev_alloc(c, &c->d_gvdi_dep, (size_t)c->N * c->cblockE)) ||
-                    (rc = dev_alloc(c, &c->d_gvdi_cnt, (size_t)c->N * c->stripPx)))
+                if ((rc = c->d_gvdi_col.alloc(c, (size_t)c->N * c->cblockE)) ||
+                    (rc = c->d_gvdi_dep.alloc(c, (size_t)c->N * c->cblockE)) ||
+                    (rc = c->d_gvdi_cnt.alloc(c, (size_t)c->N * c->stripPx)))
                     return bail(rc);
-            } else if ((rc = dev_alloc(c, &c->d_cvdi_col, c->cblockE)) || (rc = dev_alloc(c, &c->d_cvdi_dep, c->cblockE)) ||
-                       (rc = dev_alloc(c, &c->d_cvdi_cnt, c->stripPx))) {
+            } else if ((rc = c->d_cvdi_col.alloc(c, c->cblockE)) || (rc = c->d_cvdi_dep.alloc(c, c->cblockE)) ||
+                       (rc = c->d_cvdi_cnt.alloc(c, c->stripPx))) {
                 return bail(rc);
             }
         }
@@ -756,12 +759,12 @@ int insitu_create(const insitu_config* cfg, insitu_ctx** out) {
         c->plainBlock = (size_t)c->rows * (size_t)c->W;
         c->stripPx = c->plainBlock;
         const size_t sendPx = (size_t)c->N * (size_t)c->B * c->plainBlock;
-        if ((rc = dev_alloc(c, &c->d_pcol_send, sendPx)) || (rc = dev_alloc(c, &c->d_pdep_send, sendPx))) return bail(rc);
+        if ((rc = c->d_pcol_send.alloc(c, sendPx)) || (rc = c->d_pdep_send.alloc(c, sendPx))) return bail(rc);
         if (c->N > 1)
-            if ((rc = dev_alloc(c, &c->d_pcol_recv, sendPx)) || (rc = dev_alloc(c, &c->d_pdep_recv, sendPx))) return bail(rc);
+            if ((rc = c->d_pcol_recv.alloc(c, sendPx)) || (rc = c->d_pdep_recv.alloc(c, sendPx))) return bail(rc);
         if (is_root(c)) {
-            if ((rc = dev_alloc(c, &c->d_gather, (size_t)c->N * c->stripPx))) return bail(rc);
-        } else if ((rc = dev_alloc(c, &c->d_strip, c->stripPx))) {
+            if ((rc = c->d_gather.alloc(c, (size_t)c->N * c->stripPx))) return bail(rc);
+        } else if ((rc = c->d_strip.alloc(c, c->stripPx))) {
             return bail(rc);
         }
     }
@@ -887,13 +890,8 @@ int insitu_set_brick(insitu_ctx* c, int slot, const void* data, int dtype, const
     const size_t nb = (size_t)((dims[0] + 7) / 8) * (size_t)((dims[1] + 7) / 8) * (size_t)((dims[2] + 7) / 8);
     if (nb * 729 >= (size_t)1 << 32) return fail(c, -1, "insitu_set_brick: blocked brick exceeds 2^32 voxels");
     const size_t bytes = nb * 729 * dtype_size(dtype);   // blocked layout with halo (insitu_sampling.h)
-    if (b.bytes != bytes) {
-        if (b.d) HIPCHK(c, hipFree(b.d));
-        b.d = nullptr;
-        b.bytes = 0;
-        HIPCHK(c, hipMalloc(&b.d, bytes));
-        b.bytes = bytes;
-    }
+    if (b.d.count() != bytes)
+        if (int rc = b.d.alloc(c, bytes)) return rc;
     if (!mat4_inverse(model, b.im)) return fail(c, -1, "insitu_set_brick: model matrix is singular");
     b.dtype = dtype;
     std::memcpy(b.dims, dims, sizeof b.dims);
@@ -913,13 +911,9 @@ int insitu_set_brick(insitu_ctx* c, int slot, const void* data, int dtype, const
         // the staging buffer is kept across calls: the reference re-uploads every grid every 20 frames
         // (DistributedVolumeRenderer.kt:521-527); a pinned source makes the copy a DMA at link speed
         const size_t src_bytes = vox * dtype_size(dtype);
-        if (c->staging_bytes < src_bytes) {
+        if (c->d_staging.count() < src_bytes) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->d_staging) HIPCHK(c, hipFree(c->d_staging));
-            c->d_staging = nullptr;
-            c->staging_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->d_staging, src_bytes));
-            c->staging_bytes = src_bytes;
+            if (int rc = c->d_staging.reserve(c, src_bytes)) return rc;
         }
         hipError_t e = hipMemcpyAsync(c->d_staging, data, src_bytes, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = launch_brick_ingest(c->d_staging, b.d, dtype, dims[0], dims[1], dims[2], c->stream);
@@ -947,18 +941,13 @@ int insitu_set_transfer(insitu_ctx* c, const float* tf, int n_tf, const float* c
                                    " texels need " + std::to_string(need) + " bytes of LDS per block; the device has " +
                                    std::to_string(max_lds));
     }
-    if (n_tf != c->n_tf) {
-        if (c->d_tf) HIPCHK(c, hipFree(c->d_tf));
-        c->d_tf = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_tf, sizeof(float) * n_tf));
-        c->n_tf = n_tf;
-    }
-    if (n_cm != c->n_cm) {
-        if (c->d_cmap) HIPCHK(c, hipFree(c->d_cmap));
-        c->d_cmap = nullptr;
-        HIPCHK(c, hipMalloc(&c->d_cmap, sizeof(float) * 4 * n_cm));
-        c->n_cm = n_cm;
-    }
+    // (the LUTs are sized exactly: a size that differs re-allocates; a failure leaves that LUT unset)
+    if (c->d_tf.count() != (size_t)n_tf)
+        if (int rc = c->d_tf.alloc(c, (size_t)n_tf)) return rc;
+    c->n_tf = n_tf;
+    if (c->d_cmap.count() != 4 * (size_t)n_cm)
+        if (int rc = c->d_cmap.alloc(c, 4 * (size_t)n_cm)) return rc;
+    c->n_cm = n_cm;
     // the colour bound of the filtered decisions' margin (vdi_generate.hip, filter_margin)
     double cm_max = 0.0, tf_max = 0.0;
     bool finite = true;
@@ -996,8 +985,16 @@ static BrickDesc brick_desc(const insitu_ctx* c, const Brick& b) {
     return d;
 }
 
-int insitu_set_camera(insitu_ctx* c, const insitu_camera* cam) {
-    if (!c) return fail(nullptr, -1, "insitu_set_camera: null context");
+namespace {
+
+// a checked camera as a frame keeps it: the matrix products the kernels and the compositors take
+struct FrameCamera {
+    float ipv[16], pv[16], view[16];
+    float nw, fwnw, tmax;
+};
+
+// the camera set-up of insitu_set_camera and of every render; writes *m only when the camera is accepted
+int camera_matrices(insitu_ctx* c, const insitu_camera* cam, FrameCamera* m) {
     if (!cam) return fail(c, -1, "insitu_set_camera: null camera");
     float iv[16], ip[16];
     if (cam->has_inverses) {
@@ -1006,18 +1003,24 @@ int insitu_set_camera(insitu_ctx* c, const insitu_camera* cam) {
     } else if (!mat4_inverse(cam->view, iv) || !mat4_inverse(cam->proj, ip)) {
         return fail(c, -1, "insitu_set_camera: view or projection matrix is singular");
     }
-    mat4_mul_f(iv, ip, c->cur->ipv);                // VDIGenerator.comp:289 (ipvG of accumulateSupseg)
-    mat4_mul_f(cam->proj, cam->view, c->cur->pv);   // VDIGenerator.comp:290
-    std::memcpy(c->cur->view, cam->view, sizeof c->cur->view);
-    c->camera_set = true;
+    mat4_mul_f(iv, ip, m->ipv);                // VDIGenerator.comp:289 (ipvG of accumulateSupseg)
+    mat4_mul_f(cam->proj, cam->view, m->pv);   // VDIGenerator.comp:290
+    std::memcpy(m->view, cam->view, sizeof m->view);
+    m->nw = cam->nw; m->fwnw = cam->fwnw; m->tmax = cam->tmax;
     return 0;
 }
 
-int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
-    if (!c) return fail(nullptr, -1, "insitu_render: null context");
+void set_slot_camera(insitu_ctx* c, FrameSlot& f, const FrameCamera& m) {
+    std::memcpy(f.ipv, m.ipv, sizeof f.ipv);
+    std::memcpy(f.pv, m.pv, sizeof f.pv);
+    std::memcpy(f.view, m.view, sizeof f.view);
+    c->camera_set = true;
+}
+
+// everything that rejects a render, pipelined or not, before anything is enqueued or changed: *m is the camera
+// render_frame takes
+int render_check(insitu_ctx* c, const insitu_camera* cam, FrameCamera* m) {
     if (!cam) return fail(c, -1, "insitu_render: null camera");
-    if (c->pipe_inflight && !c->s_sample)
-        return fail(c, -1, "insitu_render: a pipelined frame is in flight (insitu_pipeline_flush first)");
     if (!c->d_tf) return fail(c, -1, "insitu_render: transfer function not set");
     for (int b = 0; b < c->B; ++b) {
         if (!c->bricks[b].valid) return fail(c, -1, "insitu_render: brick slot " + std::to_string(b) + " not set");
@@ -1025,20 +1028,32 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
             return fail(c, -1, "insitu_render: all bricks of a rank must share one voxel type");
     }
     if (!(cam->nw > 0.0f)) return fail(c, -1, "insitu_render: nw must be > 0");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    int rc = insitu_set_camera(c, cam);
-    if (rc) return rc;
-    FrameSlot& f = *c->cur;
+    return camera_matrices(c, cam, m);
+}
+
+// where a render enqueues.  Unpipelined: both streams are the context stream and nothing gates the first pass.
+// Pipelined (insitu_frame_pipelined): the first pass on the sampling stream, behind the gate -- placed between
+// the frame's prepare (counters, tile keys and their sort: the slot's own buffers) and its sampling kernel, so
+// the prepare's launches run ahead of it -- and the search on the slot's search stream.
+struct RenderPlan {
+    hipStream_t first = nullptr;    // the first pass
+    hipStream_t search = nullptr;   // the search and what follows it
+    bool pipelined = false;
+    unsigned long long* gate_flag = nullptr;         // the first pass waits for *gate_flag >= gate_value (mode 1) ...
+    unsigned long long gate_value = 0;
+    hipEvent_t gate_event = nullptr;                 // ... or for this event (mode 0), or for neither
+};
+
+// the render of a checked camera (render_check) into slot f
+int render_frame(insitu_ctx* c, FrameSlot& f, const FrameCamera& cam, const RenderPlan& plan) {
+    set_slot_camera(c, f, cam);
     TransferDesc xf{c->d_tf, c->n_tf, c->d_cmap, c->n_cm, c->cmag};
-    HIPCHK(c, wait_peer_reads(c));
+    const hipStream_t ss = plan.first, sr = plan.search;
+    const bool pipelined = plan.pipelined;
+    HIPCHK(c, wait_peer_reads(c, ss));
     c->ingest_batch = false;
-    // the first pass runs on s_sample (a pipelined frame: the sampling stream, behind the trigger the caller
-    // enqueued there), the search and the rest on `stream`
-    hipStream_t ss = c->s_sample ? c->s_sample : c->stream;
-    const bool pipelined = c->s_sample != nullptr;
-    hipStream_t sr = pipelined ? f.search_stream : c->stream;   // the search and what follows it
     f.pipelined = pipelined;
-    if (!pipelined) record_on(c, EvRenderStart, ss);   // (pipelined: at the trigger, below)
+    if (!pipelined) record(f, EvRenderStart, ss);   // (pipelined: at the gate, below)
     if (c->mode == INSITU_MODE_VDI) {
         const size_t oct = (size_t)c->BV * (size_t)c->S * (size_t)c->ncx * (size_t)c->ncy;
         if (oct) HIPCHK(c, hipMemsetAsync(f.octree, 0, oct * sizeof(uint32_t), ss));   // GridCellsToZero.comp
@@ -1048,11 +1063,11 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
             HIPCHK(c, hipStreamSynchronize(ss));
             HIPCHK(c, hipStreamSynchronize(sr));
-            if (cache_realloc(c, grow) != hipSuccess) {
+            if (cache_realloc(f, grow) != hipSuccess) {
                 // keep what fits (the rest re-samples): half the request, never less than the cache
                 // that worked, and at most that from now on
                 const size_t keep = std::max(old, grow / 2);
-                if (cache_realloc(c, keep) != hipSuccess) HIPCHK(c, cache_realloc(c, old));
+                if (cache_realloc(f, keep) != hipSuccess) HIPCHK(c, cache_realloc(f, old));
                 c->cache_max_chunks = f.cache_chunks;
             }
         }
@@ -1062,8 +1077,8 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
         std::memcpy(p.ipv, f.ipv, sizeof p.ipv);
         std::memcpy(p.pv, f.pv, sizeof p.pv);
         std::memcpy(p.view, f.view, sizeof p.view);
-        p.nw = cam->nw;
-        p.tmax = cam->tmax;
+        p.nw = cam.nw;
+        p.tmax = cam.tmax;
         p.W = c->W; p.H = c->H; p.S = c->S;
         p.strip_w = c->strip_w; p.strip_tiles = c->strip_tiles; p.nstrips = c->N; p.B = c->BV;
         p.nvolumes = c->BV != c->B ? c->B : 0;
@@ -1119,7 +1134,7 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
         }
         if (pipelined && f.cache && c->pipe_flag && c->pipe_trigger == 1) {
             p.pipe_flag = c->pipe_flag + f.flag_index;   // this search's queue drain starts the next first pass
-            p.pipe_seq = c->pipe_seq;
+            p.pipe_seq = f.flag_value + 1;
         }
         // counters zeroed, tile keys (and, on a default cache's first frame, the frame's cache demand) sorted
         p.measure_cache = (c->cache_adaptive && !f.cache_sized && p.nvolumes == 0) ? 1 : 0;
@@ -1133,19 +1148,19 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
             HIPCHK(c, hipStreamSynchronize(ss));
             f.cache_sized = true;
             const size_t want = std::min((size_t)(need + need / 4 + 64), c->cache_max_chunks);
-            if (want > f.cache_chunks) HIPCHK(c, cache_realloc(c, want));
+            if (want > f.cache_chunks) HIPCHK(c, cache_realloc(f, want));
             p.cache = f.cache;
             p.cache_chunks = f.cache_chunks;
         }
         if (pipelined) {
-            // the trigger (insitu_frame_pipelined): the prepare above only touches this slot's buffers, so its
+            // the gate (insitu_frame_pipelined): the prepare above only touches this slot's buffers, so its
             // small launches are already queued when the previous frame's search lets the first pass start;
             // the frame's render time and latency count from here
-            if (c->trig_flag)
-                HIPCHK(c, hipStreamWaitValue64(ss, c->trig_flag, c->trig_value, hipStreamWaitValueGte));
-            else if (c->trig_event)
-                HIPCHK(c, hipStreamWaitEvent(ss, c->trig_event, 0));
-            record_on(c, EvRenderStart, ss);
+            if (plan.gate_flag)
+                HIPCHK(c, hipStreamWaitValue64(ss, plan.gate_flag, plan.gate_value, hipStreamWaitValueGte));
+            else if (plan.gate_event)
+                HIPCHK(c, hipStreamWaitEvent(ss, plan.gate_event, 0));
+            record(f, EvRenderStart, ss);
         }
         if (c->d_dbg && !pipelined) {
             HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, c->dbg_entries * 32, ss));
@@ -1160,8 +1175,11 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
         if (pipelined) {
             // the next frame's trigger: the search is over (mode 0), or -- the flag's safety net when no wave
             // crossed the trigger point (an empty queue) -- its value is reached (mode 1)
-            record_on(c, EvSearchEnd, sr);
-            if (p.pipe_flag) HIPCHK(c, hipStreamWriteValue64(sr, p.pipe_flag, c->pipe_seq, 0));
+            record(f, EvSearchEnd, sr);
+            if (p.pipe_flag) {
+                HIPCHK(c, hipStreamWriteValue64(sr, p.pipe_flag, p.pipe_seq, 0));
+                f.flag_value = p.pipe_seq;   // what the next frame's gate waits for: its store is enqueued
+            }
         }
         HIPCHK(c, launch_vdi_finish(p, sr));
         if (f.h_ctr) {   // the frame's counters, read on the host after the next synchronisation
@@ -1172,33 +1190,30 @@ int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
         // variable-length exchange: the stored supersegments of the blocks bound for the other
         // ranks are packed as part of producing the send buffers (timed as the exchange); a pipelined frame
         // packs them with its completion, where the compact buffers are free
-        if (c->N > 1 && !pipelined) HIPCHK(c, compact_enqueue(c));
+        if (c->N > 1 && !pipelined) HIPCHK(c, compact_enqueue(c, f, sr));
         c->lists_from_reference = false;
     } else {
         PlainGenParams p{};
         for (int b = 0; b < c->B; ++b) p.bricks[b] = brick_desc(c, c->bricks[b]);
         p.xfer = xf;
         std::memcpy(p.ipv, f.ipv, sizeof p.ipv);
-        p.nw = cam->nw; p.fwnw = cam->fwnw; p.tmax = cam->tmax;
+        p.nw = cam.nw; p.fwnw = cam.fwnw; p.tmax = cam.tmax;
         p.dim0 = c->W; p.dim1 = c->H; p.rows = c->rows;
         p.nstrips = c->N; p.B = c->B;
         p.color = c->d_pcol_send;
         p.depth = c->d_pdep_send;
-        HIPCHK(c, launch_plain_generate(p, c->stream));
+        HIPCHK(c, launch_plain_generate(p, sr));
     }
-    record_on(c, EvRenderEnd, sr);
+    record(f, EvRenderEnd, sr);
     f.rendered = true;
     f.composited = false;
     f.exchanged = false;
     return 0;
 }
 
-int insitu_exchange(insitu_ctx* c) {
-    if (!c) return fail(nullptr, -1, "insitu_exchange: null context");
-    if (c->pipe_inflight && !c->completing)
-        return fail(c, -1, "insitu_exchange: a pipelined frame is in flight (insitu_pipeline_flush first)");
-    if (!c->cur->rendered) return fail(c, -1, "insitu_exchange: nothing rendered");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
+// the exchange of slot f's rendered frame on stream s
+int exchange_frame(insitu_ctx* c, FrameSlot& f, hipStream_t st) {
+    if (!f.rendered) return fail(c, -1, "insitu_exchange: nothing rendered");
     c->last_exchange_entries = 0;
     c->last_exchange_bytes = 0;
     if (c->N > 1 && c->mode == INSITU_MODE_VDI) {
@@ -1214,52 +1229,52 @@ int insitu_exchange(insitu_ctx* c) {
                 const insitu_ctx* q = c->group->ranks[p];
                 if (!q) return fail(c, -1, "insitu_exchange: local group rank " + std::to_string(p) + " missing");
                 if (!q->cur->rendered || !q->cur->ev_valid[EvRenderEnd]) return fail(c, -1, "insitu_exchange: local group rank " + std::to_string(p) + " has not rendered");
-                HIPCHK(c, hipStreamWaitEvent(c->stream, q->cur->ev[EvRenderEnd], 0));
-                HIPCHK(c, hipMemcpyAsync(recv_tot + p, q->d_cursor + c->rank, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipStreamWaitEvent(st, q->cur->ev[EvRenderEnd], 0));
+                HIPCHK(c, hipMemcpyAsync(recv_tot + p, q->d_cursor + c->rank, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             }
-            HIPCHK(c, hipMemcpyAsync(send_tot, c->d_cursor, sizeof(uint32_t) * (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
-            record(c, EvCountsIn);
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            record(c, EvPayloadStart);
+            HIPCHK(c, hipMemcpyAsync(send_tot, c->d_cursor, sizeof(uint32_t) * (size_t)c->N, hipMemcpyDeviceToHost, st));
+            record(f, EvCountsIn, st);
+            HIPCHK(c, hipStreamSynchronize(st));
+            record(f, EvPayloadStart, st);
             for (int p = 0; p < c->N; ++p) {
                 if (p == c->rank) continue;
                 const insitu_ctx* q = c->group->ranks[p];
                 HIPCHK(c, hipMemcpyAsync(c->d_meta_recv + (size_t)p * c->meta_bytes, q->d_meta_send + (size_t)c->rank * q->meta_bytes,
-                                         c->meta_bytes, hipMemcpyDeviceToDevice, c->stream));
+                                         c->meta_bytes, hipMemcpyDeviceToDevice, st));
                 const size_t n = recv_tot[p];
                 if (n == 0) continue;
                 HIPCHK(c, hipMemcpyAsync(c->d_vcol_recv + (size_t)p * region, q->d_ccol_send + (size_t)c->rank * region,
-                                         n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+                                         n * sizeof(float4), hipMemcpyDeviceToDevice, st));
                 HIPCHK(c, hipMemcpyAsync(c->d_vdep_recv + (size_t)p * region, q->d_cdep_send + (size_t)c->rank * region,
-                                         n * sizeof(float2), hipMemcpyDeviceToDevice, c->stream));
+                                         n * sizeof(float2), hipMemcpyDeviceToDevice, st));
             }
         } else {
             NCCLCHK(c, ncclGroupStart());
             for (int p = 0; p < c->N; ++p) {
                 if (p == c->rank) continue;
-                NCCLCHK(c, ncclSend(c->d_cursor + p, 1, ncclUint32, p, c->comm, c->stream));
-                NCCLCHK(c, ncclRecv(c->d_cursor + c->N + p, 1, ncclUint32, p, c->comm, c->stream));
+                NCCLCHK(c, ncclSend(c->d_cursor + p, 1, ncclUint32, p, c->comm, st));
+                NCCLCHK(c, ncclRecv(c->d_cursor + c->N + p, 1, ncclUint32, p, c->comm, st));
             }
             NCCLCHK(c, ncclGroupEnd());
             HIPCHK(c, hipMemcpyAsync(c->h_tot, c->d_cursor, 2 * sizeof(uint32_t) * (size_t)c->N, hipMemcpyDeviceToHost,
-                                     c->stream));
+                                     st));
             // the host learns the receive sizes: the stream idles from here (EvCountsIn) until the payload
             // group is enqueued (EvPayloadStart) -- reported as insitu_stats.ms_exchange_sync
-            record(c, EvCountsIn);
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            record(c, EvPayloadStart);
+            record(f, EvCountsIn, st);
+            HIPCHK(c, hipStreamSynchronize(st));
+            record(f, EvPayloadStart, st);
             NCCLCHK(c, ncclGroupStart());
             for (int p = 0; p < c->N; ++p) {
                 if (p == c->rank) continue;
-                NCCLCHK(c, ncclSend(c->d_meta_send + (size_t)p * c->meta_bytes, c->meta_bytes, ncclUint8, p, c->comm, c->stream));
-                NCCLCHK(c, ncclRecv(c->d_meta_recv + (size_t)p * c->meta_bytes, c->meta_bytes, ncclUint8, p, c->comm, c->stream));
+                NCCLCHK(c, ncclSend(c->d_meta_send + (size_t)p * c->meta_bytes, c->meta_bytes, ncclUint8, p, c->comm, st));
+                NCCLCHK(c, ncclRecv(c->d_meta_recv + (size_t)p * c->meta_bytes, c->meta_bytes, ncclUint8, p, c->comm, st));
                 if (send_tot[p]) {
-                    NCCLCHK(c, ncclSend(c->d_ccol_send + (size_t)p * region, (size_t)send_tot[p] * 4, ncclFloat32, p, c->comm, c->stream));
-                    NCCLCHK(c, ncclSend(c->d_cdep_send + (size_t)p * region, (size_t)send_tot[p] * 2, ncclFloat32, p, c->comm, c->stream));
+                    NCCLCHK(c, ncclSend(c->d_ccol_send + (size_t)p * region, (size_t)send_tot[p] * 4, ncclFloat32, p, c->comm, st));
+                    NCCLCHK(c, ncclSend(c->d_cdep_send + (size_t)p * region, (size_t)send_tot[p] * 2, ncclFloat32, p, c->comm, st));
                 }
                 if (recv_tot[p]) {
-                    NCCLCHK(c, ncclRecv(c->d_vcol_recv + (size_t)p * region, (size_t)recv_tot[p] * 4, ncclFloat32, p, c->comm, c->stream));
-                    NCCLCHK(c, ncclRecv(c->d_vdep_recv + (size_t)p * region, (size_t)recv_tot[p] * 2, ncclFloat32, p, c->comm, c->stream));
+                    NCCLCHK(c, ncclRecv(c->d_vcol_recv + (size_t)p * region, (size_t)recv_tot[p] * 4, ncclFloat32, p, c->comm, st));
+                    NCCLCHK(c, ncclRecv(c->d_vdep_recv + (size_t)p * region, (size_t)recv_tot[p] * 2, ncclFloat32, p, c->comm, st));
                 }
             }
             NCCLCHK(c, ncclGroupEnd());
@@ -1276,11 +1291,11 @@ int insitu_exchange(insitu_ctx* c) {
             if (!q) return fail(c, -1, "insitu_exchange: local group rank " + std::to_string(p) + " missing");
             if (!q->cur->rendered || !q->cur->ev_valid[EvRenderEnd]) return fail(c, -1, "insitu_exchange: local group rank " + std::to_string(p) + " has not rendered");
             // the peer's render runs on its own stream (and maybe device): order my copies after it
-            HIPCHK(c, hipStreamWaitEvent(c->stream, q->cur->ev[EvRenderEnd], 0));
+            HIPCHK(c, hipStreamWaitEvent(st, q->cur->ev[EvRenderEnd], 0));
             const size_t n = (size_t)c->B * c->plainBlock;
             const size_t src = (size_t)c->rank * n, dst = (size_t)p * n;
-            HIPCHK(c, hipMemcpyAsync(c->d_pcol_recv + dst, q->d_pcol_send + src, n * 4, hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->d_pdep_recv + dst, q->d_pdep_send + src, n * 4, hipMemcpyDeviceToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->d_pcol_recv + dst, q->d_pcol_send + src, n * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipMemcpyAsync(c->d_pdep_recv + dst, q->d_pdep_send + src, n * 4, hipMemcpyDeviceToDevice, st));
         }
         c->last_exchange_bytes = (long long)(c->N - 1) * (long long)c->B * (long long)c->plainBlock * 8;
     } else if (c->N > 1) {   // plain mode: one rgba8 colour + depth texel per pixel, fixed-size blocks
@@ -1288,37 +1303,37 @@ int insitu_exchange(insitu_ctx* c) {
         for (int p = 0; p < c->N; ++p) {
             if (p == c->rank) continue;
             const size_t e = (size_t)p * (size_t)c->B * c->plainBlock, n = (size_t)c->B * c->plainBlock;
-            NCCLCHK(c, ncclSend(c->d_pcol_send + e, n, ncclUint32, p, c->comm, c->stream));
-            NCCLCHK(c, ncclRecv(c->d_pcol_recv + e, n, ncclUint32, p, c->comm, c->stream));
-            NCCLCHK(c, ncclSend(c->d_pdep_send + e, n, ncclUint32, p, c->comm, c->stream));
-            NCCLCHK(c, ncclRecv(c->d_pdep_recv + e, n, ncclUint32, p, c->comm, c->stream));
+            NCCLCHK(c, ncclSend(c->d_pcol_send + e, n, ncclUint32, p, c->comm, st));
+            NCCLCHK(c, ncclRecv(c->d_pcol_recv + e, n, ncclUint32, p, c->comm, st));
+            NCCLCHK(c, ncclSend(c->d_pdep_send + e, n, ncclUint32, p, c->comm, st));
+            NCCLCHK(c, ncclRecv(c->d_pdep_recv + e, n, ncclUint32, p, c->comm, st));
         }
         NCCLCHK(c, ncclGroupEnd());
         c->last_exchange_bytes = (long long)(c->N - 1) * (long long)c->B * (long long)c->plainBlock * 8;
     }
-    if (c->group) record(c, EvPeerReadsDone);
-    record(c, EvExchangeEnd);
-    c->cur->exchanged = true;
+    if (c->group) record(f, EvPeerReadsDone, st);
+    record(f, EvExchangeEnd, st);
+    f.exchanged = true;
     return 0;
 }
 
-namespace {
-// list v (source s = v / B, brick b = v % B) of this rank's strip, as the compositors read it
-VdiList list_of(const insitu_ctx* c, int v) {
+// list v (source s = v / B, brick b = v % B) of this rank's strip, as the compositors read it: this rank's own
+// from slot f
+VdiList list_of(const insitu_ctx* c, const FrameSlot& f, int v) {
     const int s = v / c->BV, b = v % c->BV;
     VdiList L{};
     if (c->lists_from_reference) {   // host-buffer path: reference layout converted to slots (B == 1)
         const size_t slot = (size_t)s * c->blockE;
-        L.col = (s == c->rank ? c->cur->vcol_send : c->d_vcol_recv) + slot;
-        L.dep = (s == c->rank ? c->cur->vdep_send : c->d_vdep_recv) + slot;
+        L.col = (s == c->rank ? f.vcol_send : c->d_vcol_recv) + slot;
+        L.dep = (s == c->rank ? f.vdep_send : c->d_vdep_recv) + slot;
         L.cnt16 = c->d_ref_cnt + (size_t)s * c->stripPx;
         L.cnt_pitch = c->strip_w;
         L.cnt_x0 = 0;
     } else if (s == c->rank) {       // my own strip: the generator's slots and counts
         const size_t e = ((size_t)c->rank * (size_t)c->BV + (size_t)b) * c->blockE;
-        L.col = c->cur->vcol_send + e;
-        L.dep = c->cur->vdep_send + e;
-        L.cnt16 = c->cur->seg_pending + (size_t)b * (size_t)c->W * (size_t)c->H;
+        L.col = f.vcol_send + e;
+        L.dep = f.vdep_send + e;
+        L.cnt16 = f.seg_pending + (size_t)b * (size_t)c->W * (size_t)c->H;
         L.cnt_pitch = c->W;
         L.cnt_x0 = c->rank * c->strip_w;
     } else {                         // the compact message source s sent
@@ -1332,25 +1347,21 @@ VdiList list_of(const insitu_ctx* c, int v) {
     }
     return L;
 }
-}  // namespace
 
-int insitu_composite(insitu_ctx* c) {
-    if (!c) return fail(nullptr, -1, "insitu_composite: null context");
-    if (c->pipe_inflight && !c->completing)
-        return fail(c, -1, "insitu_composite: a pipelined frame is in flight (insitu_pipeline_flush first)");
-    if (!c->cur->rendered) return fail(c, -1, "insitu_composite: nothing rendered");
+// the composite of slot f's frame into this rank's strip, on stream st
+int composite_frame(insitu_ctx* c, FrameSlot& f, hipStream_t st) {
+    if (!f.rendered) return fail(c, -1, "insitu_composite: nothing rendered");
     // with N > 1 the peers' lists arrive in insitu_exchange: without it the compact-message offsets
     // of the receive buffers are not this frame's (or never written)
-    if (c->N > 1 && !c->cur->exchanged) return fail(c, -1, "insitu_composite: call insitu_exchange first (nranks > 1)");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, wait_peer_reads(c));   // (local group: the root's gather of the last strip)
+    if (c->N > 1 && !f.exchanged) return fail(c, -1, "insitu_composite: call insitu_exchange first (nranks > 1)");
+    HIPCHK(c, wait_peer_reads(c, st));   // (local group: the root's gather of the last strip)
     uint32_t* out = is_root(c) ? c->d_gather + (size_t)c->rank * c->stripPx : c->d_strip;
     if (c->mode == INSITU_MODE_VDI && c->composite_vdi) {
         CompositeParams p{};   // VDICompositor.comp (DistributedVolumes.kt:424-439)
         p.V = c->V; p.S = c->S; p.S_out = c->S_out; p.H = c->H; p.W = c->W;
         p.strip_w = c->strip_w; p.strip_tiles = c->strip_tiles; p.x_offset = c->rank * c->strip_w;
-        std::memcpy(p.ipv, c->cur->ipv, sizeof p.ipv);
-        for (int v = 0; v < c->V; ++v) p.lists[v] = list_of(c, v);
+        std::memcpy(p.ipv, f.ipv, sizeof p.ipv);
+        for (int v = 0; v < c->V; ++v) p.lists[v] = list_of(c, f, v);
         p.out_color = cvdi_col(c);
         p.out_depth = cvdi_dep(c);
         p.out_count = cvdi_cnt(c);
@@ -1363,43 +1374,40 @@ int insitu_composite(insitu_ctx* c) {
             const unsigned long long dem = c->cseq_demand, old = c->cseq_cap;
             if (dem > old && old < c->cseq_max) {
                 const unsigned long long want = std::min(dem + dem / 4, c->cseq_max);
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                HIPCHK(c, hipFree(c->d_cseq));
-                c->d_cseq = nullptr;
+                HIPCHK(c, hipStreamSynchronize(st));
+                c->d_cseq.reset();
                 c->cseq_cap = 0;
                 // the request, else half of it, else the cache that worked (and that size from now on)
                 for (unsigned long long sz : {want, std::max(old, want / 2), old}) {
-                    if (sz && hipMalloc(&c->d_cseq, (size_t)sz * 16 * kCompEntryF4) == hipSuccess) {
+                    if (sz && c->d_cseq.try_alloc((size_t)sz * kCompEntryF4) == hipSuccess) {
                         c->cseq_cap = sz;
                         break;
                     }
-                    (void)hipGetLastError();
-                    c->d_cseq = nullptr;
                 }
                 if (c->cseq_cap < want) c->cseq_max = c->cseq_cap;
                 if (!c->d_cseq) return fail(c, -5, "insitu_composite: re-allocating the merge cache failed");
             }
             if (c->d_cseq) {
-                HIPCHK(c, hipMemsetAsync(c->d_cseq_cursor, 0, sizeof(unsigned long long), c->stream));
+                HIPCHK(c, hipMemsetAsync(c->d_cseq_cursor, 0, sizeof(unsigned long long), st));
                 p.seq = c->d_cseq;
                 p.seq_cursor = c->d_cseq_cursor;
                 p.seq_cap = c->cseq_cap;
             }
         }
-        HIPCHK(c, launch_vdi_composite(p, c->stream));
+        HIPCHK(c, launch_vdi_composite(p, st));
         if (p.seq) {
             HIPCHK(c, hipMemcpyAsync(c->h_cseq_demand, c->d_cseq_cursor, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                     c->stream));
+                                     st));
             c->cseq_pending = true;   // observed after the next synchronisation (cache_observe)
         }
     } else if (c->mode == INSITU_MODE_VDI) {
         FlattenParams p{};
         p.V = c->V; p.S = c->S; p.H = c->H; p.W = c->W;
         p.strip_w = c->strip_w; p.strip_tiles = c->strip_tiles; p.x_offset = c->rank * c->strip_w;
-        std::memcpy(p.ipv, c->cur->ipv, sizeof p.ipv);
-        for (int v = 0; v < c->V; ++v) p.lists[v] = list_of(c, v);
+        std::memcpy(p.ipv, f.ipv, sizeof p.ipv);
+        for (int v = 0; v < c->V; ++v) p.lists[v] = list_of(c, f, v);
         p.out = out;
-        HIPCHK(c, launch_vdi_flatten(p, c->stream));
+        HIPCHK(c, launch_vdi_flatten(p, st));
     } else {
         PlainCompParams p{};
         p.V = c->V; p.dim0 = c->W; p.rows = c->rows;
@@ -1419,36 +1427,33 @@ int insitu_composite(insitu_ctx* c) {
             }
         }
         p.out = out;
-        HIPCHK(c, launch_plain_composite(p, c->stream));
+        HIPCHK(c, launch_plain_composite(p, st));
     }
-    record(c, EvCompositeEnd);
-    c->cur->composited = true;
+    record(f, EvCompositeEnd, st);
+    f.composited = true;
     return 0;
 }
 
-int insitu_gather(insitu_ctx* c, void* host_out, size_t cap) {
-    if (!c) return fail(nullptr, -1, "insitu_gather: null context");
-    if (c->pipe_inflight && !c->completing)
-        return fail(c, -1, "insitu_gather: a pipelined frame is in flight (insitu_pipeline_flush first)");
-    if (!c->cur->composited) return fail(c, -1, "insitu_gather: nothing composited");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
+// the gather of slot f's composited frame on stream st (+ the root's image to host_out); blocks until it is done
+int gather_frame(insitu_ctx* c, FrameSlot& f, hipStream_t st, void* host_out, size_t cap) {
+    if (!f.composited) return fail(c, -1, "insitu_gather: nothing composited");
     if (c->N > 1 && c->group) {   // in-process: the root pulls every peer's strip
         if (is_root(c)) {
             for (int p = 1; p < c->N; ++p) {
                 const insitu_ctx* q = c->group->ranks[p];
                 if (!q) return fail(c, -1, "insitu_gather: local group rank " + std::to_string(p) + " missing");
                 if (!q->cur->composited || !q->cur->ev_valid[EvCompositeEnd]) return fail(c, -1, "insitu_gather: local group rank " + std::to_string(p) + " has not composited");
-                HIPCHK(c, hipStreamWaitEvent(c->stream, q->cur->ev[EvCompositeEnd], 0));   // the peer's composite, its stream
+                HIPCHK(c, hipStreamWaitEvent(st, q->cur->ev[EvCompositeEnd], 0));   // the peer's composite, its stream
                 if (c->composite_vdi) {
                     HIPCHK(c, hipMemcpyAsync(c->d_gvdi_col + (size_t)p * c->cblockE, q->d_cvdi_col, c->cblockE * sizeof(float4),
-                                             hipMemcpyDeviceToDevice, c->stream));
+                                             hipMemcpyDeviceToDevice, st));
                     HIPCHK(c, hipMemcpyAsync(c->d_gvdi_dep + (size_t)p * c->cblockE, q->d_cvdi_dep, c->cblockE * sizeof(float2),
-                                             hipMemcpyDeviceToDevice, c->stream));
+                                             hipMemcpyDeviceToDevice, st));
                     HIPCHK(c, hipMemcpyAsync(c->d_gvdi_cnt + (size_t)p * c->stripPx, q->d_cvdi_cnt, c->stripPx * sizeof(uint16_t),
-                                             hipMemcpyDeviceToDevice, c->stream));
+                                             hipMemcpyDeviceToDevice, st));
                 } else {
                     HIPCHK(c, hipMemcpyAsync(c->d_gather + (size_t)p * c->stripPx, q->d_strip, c->stripPx * 4,
-                                             hipMemcpyDeviceToDevice, c->stream));
+                                             hipMemcpyDeviceToDevice, st));
                 }
             }
         }
@@ -1457,74 +1462,64 @@ int insitu_gather(insitu_ctx* c, void* host_out, size_t cap) {
         if (is_root(c)) {
             for (int p = 1; p < c->N; ++p) {
                 NCCLCHK(c, ncclRecv(c->d_gvdi_col + (size_t)p * c->cblockE, c->cblockE * 4, ncclFloat32, p, c->comm,
-                                    c->stream));
+                                    st));
                 NCCLCHK(c, ncclRecv(c->d_gvdi_dep + (size_t)p * c->cblockE, c->cblockE * 2, ncclFloat32, p, c->comm,
-                                    c->stream));
+                                    st));
                 NCCLCHK(c, ncclRecv(c->d_gvdi_cnt + (size_t)p * c->stripPx, c->stripPx * sizeof(uint16_t), ncclUint8, p,
-                                    c->comm, c->stream));
+                                    c->comm, st));
             }
         } else {
-            NCCLCHK(c, ncclSend(c->d_cvdi_col, c->cblockE * 4, ncclFloat32, 0, c->comm, c->stream));
-            NCCLCHK(c, ncclSend(c->d_cvdi_dep, c->cblockE * 2, ncclFloat32, 0, c->comm, c->stream));
-            NCCLCHK(c, ncclSend(c->d_cvdi_cnt, c->stripPx * sizeof(uint16_t), ncclUint8, 0, c->comm, c->stream));
+            NCCLCHK(c, ncclSend(c->d_cvdi_col, c->cblockE * 4, ncclFloat32, 0, c->comm, st));
+            NCCLCHK(c, ncclSend(c->d_cvdi_dep, c->cblockE * 2, ncclFloat32, 0, c->comm, st));
+            NCCLCHK(c, ncclSend(c->d_cvdi_cnt, c->stripPx * sizeof(uint16_t), ncclUint8, 0, c->comm, st));
         }
         NCCLCHK(c, ncclGroupEnd());
     } else if (c->N > 1) {
         NCCLCHK(c, ncclGroupStart());
         if (is_root(c)) {
             for (int p = 1; p < c->N; ++p)
-                NCCLCHK(c, ncclRecv(c->d_gather + (size_t)p * c->stripPx, c->stripPx, ncclUint32, p, c->comm, c->stream));
+                NCCLCHK(c, ncclRecv(c->d_gather + (size_t)p * c->stripPx, c->stripPx, ncclUint32, p, c->comm, st));
         } else {
-            NCCLCHK(c, ncclSend(c->d_strip, c->stripPx, ncclUint32, 0, c->comm, c->stream));
+            NCCLCHK(c, ncclSend(c->d_strip, c->stripPx, ncclUint32, 0, c->comm, st));
         }
         NCCLCHK(c, ncclGroupEnd());
     }
     if (is_root(c) && c->composite_vdi) {
         // the root's image: each gathered composited strip flattened front to back (accumulateSupseg)
         for (int p = 0; p < c->N; ++p) {
-            FlattenParams f{};
-            f.V = 1; f.S = c->S_out; f.H = c->H; f.W = c->W;
-            f.strip_w = c->strip_w; f.strip_tiles = c->strip_tiles; f.x_offset = p * c->strip_w;
-            std::memcpy(f.ipv, c->cur->ipv, sizeof f.ipv);
-            f.lists[0].col = c->d_gvdi_col + (size_t)p * c->cblockE;
-            f.lists[0].dep = c->d_gvdi_dep + (size_t)p * c->cblockE;
-            f.lists[0].cnt16 = c->d_gvdi_cnt + (size_t)p * c->stripPx;   // (slots past the count: not written)
-            f.lists[0].cnt_pitch = c->strip_w;
-            f.lists[0].cnt_x0 = 0;
-            f.out = c->d_gather + (size_t)p * c->stripPx;
-            HIPCHK(c, launch_vdi_flatten(f, c->stream));
+            FlattenParams fp{};
+            fp.V = 1; fp.S = c->S_out; fp.H = c->H; fp.W = c->W;
+            fp.strip_w = c->strip_w; fp.strip_tiles = c->strip_tiles; fp.x_offset = p * c->strip_w;
+            std::memcpy(fp.ipv, f.ipv, sizeof fp.ipv);
+            fp.lists[0].col = c->d_gvdi_col + (size_t)p * c->cblockE;
+            fp.lists[0].dep = c->d_gvdi_dep + (size_t)p * c->cblockE;
+            fp.lists[0].cnt16 = c->d_gvdi_cnt + (size_t)p * c->stripPx;   // (slots past the count: not written)
+            fp.lists[0].cnt_pitch = c->strip_w;
+            fp.lists[0].cnt_x0 = 0;
+            fp.out = c->d_gather + (size_t)p * c->stripPx;
+            HIPCHK(c, launch_vdi_flatten(fp, st));
         }
     }
     if (is_root(c) && c->composite_vdi) {   // what insitu_view_bind(INSITU_VIEW_GATHERED) takes, and its camera
         c->gvdi_valid = true;
-        std::memcpy(c->gvdi_pv, c->cur->pv, sizeof c->gvdi_pv);
+        std::memcpy(c->gvdi_pv, f.pv, sizeof c->gvdi_pv);
     }
     if (is_root(c) && c->mode == INSITU_MODE_VDI)
-        HIPCHK(c, launch_assemble_columns(c->d_gather, c->N, c->H, c->strip_w, c->d_image, c->stream));
-    if (c->group && is_root(c)) record(c, EvPeerReadsDone);
-    record(c, EvGatherEnd);
+        HIPCHK(c, launch_assemble_columns(c->d_gather, c->N, c->H, c->strip_w, c->d_image, st));
+    if (c->group && is_root(c)) record(f, EvPeerReadsDone, st);
+    record(f, EvGatherEnd, st);
     if (is_root(c) && host_out) {
         const size_t bytes = (size_t)c->W * (size_t)c->H * 4;
         if (cap < bytes) return fail(c, -1, "insitu_gather: output buffer too small");
         const void* src = c->mode == INSITU_MODE_VDI ? (const void*)c->d_image : (const void*)c->d_gather;
-        HIPCHK(c, hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, c->stream));
-        record(c, EvImageOnHost);
+        HIPCHK(c, hipMemcpyAsync(host_out, src, bytes, hipMemcpyDeviceToHost, st));
+        record(f, EvImageOnHost, st);
     } else {
-        c->cur->ev_valid[EvImageOnHost] = false;
+        f.ev_valid[EvImageOnHost] = false;
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return check_fault(c);
+    HIPCHK(c, hipStreamSynchronize(st));
+    return check_fault(c, f);
 }
-
-int insitu_frame(insitu_ctx* c, const insitu_camera* cam, void* host_out, size_t cap) {
-    int rc;
-    if ((rc = insitu_render(c, cam))) return rc;
-    if ((rc = insitu_exchange(c))) return rc;
-    if ((rc = insitu_composite(c))) return rc;
-    return insitu_gather(c, host_out, cap);
-}
-
-namespace {
 
 // the second frame slot, the sampling and completion streams and the trigger flag (first pipelined frame)
 int pipeline_setup(insitu_ctx* c) {
@@ -1542,7 +1537,7 @@ int pipeline_setup(insitu_ctx* c) {
     if (hipDeviceGetAttribute(&can_wait, hipDeviceAttributeCanUseStreamWaitValue, c->cfg.device) != hipSuccess) can_wait = 0;
     c->pipe_wait_value = can_wait != 0;
     if (c->pipe_wait_value) {
-        if (int rc = dev_alloc(c, &c->pipe_flag, 2)) return rc;
+        if (int rc = c->pipe_flag.alloc(c, 2)) return rc;
         HIPCHK(c, hipMemset(c->pipe_flag, 0, 2 * sizeof(unsigned long long)));
     }
     // the second slot starts with the cache size the first one has reached
@@ -1552,73 +1547,129 @@ int pipeline_setup(insitu_ctx* c) {
     return 0;
 }
 
-// the stages of the current slot's frame after its render, on the completion stream: compaction (N > 1),
-// exchange, composite, gather (+ the root's image to host_out); blocks until they are done
-int pipeline_complete(insitu_ctx* c, void* host_out, size_t cap) {
-    StreamScope scope(c, c->pipe_comp);
-    c->completing = true;
-    int rc = 0;
-    if (c->cur->ev_valid[EvRenderEnd] && hipStreamWaitEvent(c->stream, c->cur->ev[EvRenderEnd], 0) != hipSuccess)
-        rc = fail(c, -3, "insitu_frame_pipelined: hipStreamWaitEvent failed");
-    if (!rc && c->N > 1) {
-        hipError_t e = compact_enqueue(c);
-        if (e != hipSuccess) rc = fail(c, -3, std::string("vdi_compact_kernel: ") + hipGetErrorString(e));
+// the stages of slot f's frame after its render, on the completion stream: compaction (N > 1), exchange,
+// composite, gather (+ the root's image to host_out); blocks until they are done
+int pipeline_complete(insitu_ctx* c, FrameSlot& f, void* host_out, size_t cap) {
+    const hipStream_t st = c->pipe_comp;
+    if (f.ev_valid[EvRenderEnd] && hipStreamWaitEvent(st, f.ev[EvRenderEnd], 0) != hipSuccess)
+        return fail(c, -3, "insitu_frame_pipelined: hipStreamWaitEvent failed");
+    if (c->N > 1) {
+        hipError_t e = compact_enqueue(c, f, st);
+        if (e != hipSuccess) return fail(c, -3, std::string("vdi_compact_kernel: ") + hipGetErrorString(e));
     }
-    if (!rc) rc = insitu_exchange(c);
-    if (!rc) rc = insitu_composite(c);
-    if (!rc) {
-        record(c, EvSlotFree);   // (recorded before gather's synchronisation: the slot may be rendered into after it)
-        rc = insitu_gather(c, host_out, cap);
-    }
-    c->completing = false;
-    return rc;
+    int rc = exchange_frame(c, f, st);
+    if (!rc) rc = composite_frame(c, f, st);
+    if (rc) return rc;
+    record(f, EvSlotFree, st);   // (recorded before gather's synchronisation: the slot may be rendered into after it)
+    return gather_frame(c, f, st, host_out, cap);
 }
 
 }  // namespace
 
+// The unpipelined stages work on the completed frame's slot and the context stream, and refuse while a pipelined
+// frame is in flight.
+int insitu_set_camera(insitu_ctx* c, const insitu_camera* cam) {
+    if (!c) return fail(nullptr, -1, "insitu_set_camera: null context");
+    FrameCamera m;
+    if (int rc = camera_matrices(c, cam, &m)) return rc;
+    set_slot_camera(c, *c->cur, m);
+    return 0;
+}
+
+int insitu_render(insitu_ctx* c, const insitu_camera* cam) {
+    if (!c) return fail(nullptr, -1, "insitu_render: null context");
+    if (!cam) return fail(c, -1, "insitu_render: null camera");
+    if (c->pipe_inflight)
+        return fail(c, -1, "insitu_render: a pipelined frame is in flight (insitu_pipeline_flush first)");
+    FrameCamera m;
+    if (int rc = render_check(c, cam, &m)) return rc;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    RenderPlan plan;
+    plan.first = plan.search = c->stream;
+    return render_frame(c, *c->cur, m, plan);
+}
+
+int insitu_exchange(insitu_ctx* c) {
+    if (!c) return fail(nullptr, -1, "insitu_exchange: null context");
+    if (c->pipe_inflight)
+        return fail(c, -1, "insitu_exchange: a pipelined frame is in flight (insitu_pipeline_flush first)");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return exchange_frame(c, *c->cur, c->stream);
+}
+
+int insitu_composite(insitu_ctx* c) {
+    if (!c) return fail(nullptr, -1, "insitu_composite: null context");
+    if (c->pipe_inflight)
+        return fail(c, -1, "insitu_composite: a pipelined frame is in flight (insitu_pipeline_flush first)");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return composite_frame(c, *c->cur, c->stream);
+}
+
+int insitu_gather(insitu_ctx* c, void* host_out, size_t cap) {
+    if (!c) return fail(nullptr, -1, "insitu_gather: null context");
+    if (c->pipe_inflight)
+        return fail(c, -1, "insitu_gather: a pipelined frame is in flight (insitu_pipeline_flush first)");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    return gather_frame(c, *c->cur, c->stream, host_out, cap);
+}
+
+int insitu_frame(insitu_ctx* c, const insitu_camera* cam, void* host_out, size_t cap) {
+    int rc;
+    if ((rc = insitu_render(c, cam))) return rc;
+    if ((rc = insitu_exchange(c))) return rc;
+    if ((rc = insitu_composite(c))) return rc;
+    return insitu_gather(c, host_out, cap);
+}
+
 int insitu_frame_pipelined(insitu_ctx* c, const insitu_camera* cam, void* host_out, size_t cap, long long* done_frame) {
     if (!c) return fail(nullptr, -1, "insitu_frame_pipelined: null context");
     if (done_frame) *done_frame = -1;
+    // everything that rejects the call comes first: a rejected call has enqueued and counted nothing, so it
+    // leaves the pipeline (the frame in flight, the slots' flags and events) exactly as it was
     if (c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_frame_pipelined: VDI mode only");
     if (c->group) return fail(c, -1, "insitu_frame_pipelined: not with a local group (stages run rank by rank)");
     if (!c->cur->cache) return fail(c, -1, "insitu_frame_pipelined: needs the sample cache (sample_cache_mb >= 0)");
+    FrameCamera m;
+    if (int rc = render_check(c, cam, &m)) return rc;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (int rc = pipeline_setup(c)) return rc;
-    // 1. frame k into the current slot (its last frame is completed: EvSlotFree was synchronised)
-    hipStream_t ss = c->pipe_sample;
-    if (c->cur->ev_valid[EvSlotFree]) HIPCHK(c, hipStreamWaitEvent(ss, c->cur->ev[EvSlotFree], 0));
-    // everything enqueued on `stream` before this call -- brick ingests (a re-ingest behind the frame in flight
-    // waits for that frame's search), LUT uploads, and before the first pipelined frame whatever the context did
-    // unpipelined -- is ordered before this frame's first pass: the sampling stream is not `stream`
+    // 1. frame k into `cur` (its last frame is completed: EvSlotFree was synchronised): the first pass on the
+    // sampling stream, the search on the slot's own
+    FrameSlot& f = *c->cur;
+    RenderPlan plan;
+    plan.first = c->pipe_sample;
+    plan.search = f.search_stream;
+    plan.pipelined = true;
+    if (f.ev_valid[EvSlotFree]) HIPCHK(c, hipStreamWaitEvent(plan.first, f.ev[EvSlotFree], 0));
+    // everything enqueued on the context stream before this call -- brick ingests (a re-ingest behind the frame
+    // in flight waits for that frame's search), LUT uploads, and before the first pipelined frame whatever the
+    // context did unpipelined -- is ordered before this frame's first pass, and so before its completion
     HIPCHK(c, hipEventRecord(c->ev_gate, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(ss, c->ev_gate, 0));
+    HIPCHK(c, hipStreamWaitEvent(plan.first, c->ev_gate, 0));
     if (c->pipe_inflight) {
-        // the trigger of this frame's first pass: the previous frame's search (in `alt`) drains its queue
-        // (mode 1), or ends (mode 0); mode 2 starts it once the previous first pass is done (stream order)
-        // (enqueued by insitu_render after this frame's prepare)
+        // the gate of this frame's first pass: the previous frame's search (in `alt`) drains its queue (mode 1:
+        // the value that search stores to its slot's flag, kept in the slot; a search that stored none leaves
+        // the flag at a value already reached), or ends (mode 0); mode 2 starts it once the previous first pass
+        // is done (stream order)
         int mode = c->pipe_trigger;
         if (mode == 1 && !c->pipe_wait_value) mode = 0;
         if (mode == 1) {
-            c->trig_flag = c->pipe_flag + c->alt->flag_index;
-            c->trig_value = c->pipe_seq;
+            plan.gate_flag = c->pipe_flag + c->alt->flag_index;
+            plan.gate_value = c->alt->flag_value;
         } else if (mode == 0 && c->alt->ev_valid[EvSearchEnd]) {
-            c->trig_event = c->alt->ev[EvSearchEnd];
+            plan.gate_event = c->alt->ev[EvSearchEnd];
         }
     }
-    c->pipe_seq++;
-    c->s_sample = ss;
-    int rc = insitu_render(c, cam);
-    c->s_sample = nullptr;
-    c->trig_flag = nullptr;
-    c->trig_event = nullptr;
+    int rc = render_frame(c, f, m, plan);
     if (rc) return rc;
     const long long k = c->pipe_frames++;
-    // 2. the frame one behind (in `alt`): exchange, composite, gather -- while frame k renders
+    // 2. frame k is now the one in flight (`alt`); the frame one behind (`cur`): exchange, composite, gather --
+    // while frame k renders
     swap_slot(c);
     const bool behind = c->pipe_inflight;
-    c->pipe_inflight = true;   // (the slot now in `alt`: frame k)
+    c->pipe_inflight = true;
     if (!behind) return 0;
-    rc = pipeline_complete(c, host_out, cap);
+    rc = pipeline_complete(c, *c->cur, host_out, cap);
     if (rc) return rc;
     if (done_frame) *done_frame = k - 1;
     return 0;
@@ -1629,8 +1680,8 @@ int insitu_pipeline_flush(insitu_ctx* c, void* host_out, size_t cap, long long* 
     if (done_frame) *done_frame = -1;
     if (!c->pipe_inflight) return 0;
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    swap_slot(c);   // the frame in flight becomes current
-    int rc = pipeline_complete(c, host_out, cap);
+    swap_slot(c);   // the frame in flight becomes the completed one
+    int rc = pipeline_complete(c, *c->cur, host_out, cap);
     c->pipe_inflight = false;
     if (rc) return rc;
     if (done_frame) *done_frame = c->pipe_frames - 1;
@@ -1650,7 +1701,7 @@ int insitu_synchronize(insitu_ctx* c) {
         std::vector<unsigned long long> h(c->dbg_entries * 4);
         GenCounters gc{};
         HIPCHK(c, hipMemcpy(h.data(), c->d_dbg, h.size() * 8, hipMemcpyDeviceToHost));
-        HIPCHK(c, hipMemcpy(&gc, c->cur->counters, sizeof gc, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&gc, completed_frame(c).f.counters, sizeof gc, hipMemcpyDeviceToHost));
         if (FILE* f = std::fopen(c->dbg_path.c_str(), "wb")) {   // sizeof counters, counters, the non-empty entries
             const uint32_t hdr = (uint32_t)sizeof gc;
             std::fwrite(&hdr, sizeof hdr, 1, f);
@@ -1660,7 +1711,7 @@ int insitu_synchronize(insitu_ctx* c) {
             std::fclose(f);
         }
     }
-    return check_fault(c);
+    return check_fault(c, completed_frame(c).f);
 }
 
 size_t insitu_buffer_bytes(const insitu_ctx* c, int which) {
@@ -1670,7 +1721,7 @@ size_t insitu_buffer_bytes(const insitu_ctx* c, int which) {
     case INSITU_BUF_VDI_COLOR: return c->mode == INSITU_MODE_VDI ? px * (size_t)c->S * 16 : 0;
     case INSITU_BUF_VDI_DEPTH: return c->mode == INSITU_MODE_VDI ? px * (size_t)c->S * 8 : 0;
     case INSITU_BUF_OCTREE: return c->mode == INSITU_MODE_VDI ? (size_t)c->ncx * c->ncy * c->S * 4 : 0;
-    case INSITU_BUF_PASSES: return (c->mode == INSITU_MODE_VDI && c->cur->passes) ? px : 0;
+    case INSITU_BUF_PASSES: return (c->mode == INSITU_MODE_VDI && completed_frame(c).f.passes) ? px : 0;
     case INSITU_BUF_PLAIN_COLOR:
     case INSITU_BUF_PLAIN_DEPTH: return c->mode == INSITU_MODE_PLAIN ? px * 4 : 0;
     case INSITU_BUF_STRIP: return c->stripPx * 4;
@@ -1680,8 +1731,8 @@ size_t insitu_buffer_bytes(const insitu_ctx* c, int which) {
     case INSITU_BUF_GATHERED_COLOR: return (c->composite_vdi && is_root(c)) ? px * (size_t)c->S_out * 16 : 0;
     case INSITU_BUF_GATHERED_DEPTH: return (c->composite_vdi && is_root(c)) ? px * (size_t)c->S_out * 8 : 0;
     case INSITU_BUF_COMPOSITE_PASSES: return c->composite_vdi ? c->stripPx : 0;
-    case INSITU_BUF_RECEIVED_COLOR: return (c->mode == INSITU_MODE_VDI && c->cur->exchanged) ? (size_t)c->V * c->stripPx * c->S * 16 : 0;
-    case INSITU_BUF_RECEIVED_DEPTH: return (c->mode == INSITU_MODE_VDI && c->cur->exchanged) ? (size_t)c->V * c->stripPx * c->S * 8 : 0;
+    case INSITU_BUF_RECEIVED_COLOR: return (c->mode == INSITU_MODE_VDI && completed_frame(c).f.exchanged) ? (size_t)c->V * c->stripPx * c->S * 16 : 0;
+    case INSITU_BUF_RECEIVED_DEPTH: return (c->mode == INSITU_MODE_VDI && completed_frame(c).f.exchanged) ? (size_t)c->V * c->stripPx * c->S * 8 : 0;
     case INSITU_BUF_VIEW_COLOR: return (size_t)c->view.out_w * (size_t)c->view.out_h * 16;
     case INSITU_BUF_VIEW_IMAGE: return (size_t)c->view.out_w * (size_t)c->view.out_h * 4;
     default: return 0;
@@ -1690,7 +1741,7 @@ size_t insitu_buffer_bytes(const insitu_ctx* c, int which) {
 
 int insitu_read(insitu_ctx* c, int which, int slot, void* host_out, size_t cap) {
     if (!c) return fail(nullptr, -1, "insitu_read: null context");
-    StreamScope scope(c, read_stream(c));   // (a pipelined frame in flight: the completed frame's slot)
+    auto [f, st] = completed_frame(c);
     if (!host_out) return fail(c, -1, "insitu_read: null output");
     const size_t need = insitu_buffer_bytes(c, which);
     if (need == 0) return fail(c, -1, "insitu_read: buffer not available in this mode/rank");
@@ -1705,29 +1756,23 @@ int insitu_read(insitu_ctx* c, int which, int slot, void* host_out, size_t cap) 
     if (per_brick && (slot < 0 || slot >= (c->mode == INSITU_MODE_VDI ? c->BV : c->B)))
         return fail(c, -1, "insitu_read: slot out of range");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (int rc = check_fault(c)) return rc;
-    const FrameSlot& f = *c->cur;
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (int rc = check_fault(c, f)) return rc;
     switch (which) {
     case INSITU_BUF_VDI_COLOR:
     case INSITU_BUF_VDI_DEPTH: {
         const size_t n = (size_t)c->W * (size_t)c->H * (size_t)c->S;
-        float4* rc = nullptr;
-        float* rd = nullptr;
-        HIPCHK(c, hipMalloc(&rc, n * sizeof(float4)));
-        if (hipMalloc(&rd, n * 2 * sizeof(float)) != hipSuccess) {
-            (void)hipFree(rc);
-            return fail(c, -5, "insitu_read: scratch allocation failed");
-        }
+        DevBuf<float4> rc;   // (the scratch pair is freed at scope exit, after the synchronisation below)
+        DevBuf<float> rd;
+        HIPCHK(c, rc.try_alloc(n));
+        if (rd.try_alloc(n * 2) != hipSuccess) return fail(c, -5, "insitu_read: scratch allocation failed");
         hipError_t e = launch_vdi_to_reference(f.vcol_send, f.vdep_send, f.seg_pending,
                                                (size_t)c->W * (size_t)c->H, (size_t)c->strip_w, (size_t)c->W, c->W, 0, c->W,
-                                               c->H, c->S, c->strip_w, c->strip_tiles, c->BV, slot, rc, rd, c->stream);
+                                               c->H, c->S, c->strip_w, c->strip_tiles, c->BV, slot, rc, rd, st);
         if (e == hipSuccess)
             e = hipMemcpyAsync(host_out, which == INSITU_BUF_VDI_COLOR ? (void*)rc : (void*)rd, need,
-                               hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(rc);
-        (void)hipFree(rd);
+                               hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return fail(c, -3, std::string("insitu_read: ") + hipGetErrorString(e));
         return 0;
     }
@@ -1764,24 +1809,19 @@ int insitu_read(insitu_ctx* c, int which, int slot, void* host_out, size_t cap) 
         const bool colour = which == INSITU_BUF_COMPOSITED_COLOR || which == INSITU_BUF_GATHERED_COLOR;
         const int width = gathered ? c->W : c->strip_w;
         const size_t n = (size_t)width * (size_t)c->H * (size_t)c->S_out;
-        float4* rc = nullptr;
-        float* rd = nullptr;
-        HIPCHK(c, hipMalloc(&rc, n * sizeof(float4)));
-        if (hipMalloc(&rd, n * 2 * sizeof(float)) != hipSuccess) {
-            (void)hipFree(rc);
-            return fail(c, -5, "insitu_read: scratch allocation failed");
-        }
+        DevBuf<float4> rc;
+        DevBuf<float> rd;
+        HIPCHK(c, rc.try_alloc(n));
+        if (rd.try_alloc(n * 2) != hipSuccess) return fail(c, -5, "insitu_read: scratch allocation failed");
         // gathered: N blocks [rank] of one strip each; a single strip: one block
         // (the slots past each pixel's count are not written by the compositor: zeros here)
         hipError_t e = launch_vdi_to_reference(gathered ? c->d_gvdi_col : cvdi_col(c), gathered ? c->d_gvdi_dep : cvdi_dep(c),
                                                gathered ? c->d_gvdi_cnt : cvdi_cnt(c), 0, c->stripPx, (size_t)c->strip_w,
                                                width, 0, width, c->H, c->S_out, c->strip_w, c->strip_tiles, 1, 0, rc, rd,
-                                               c->stream);
+                                               st);
         if (e == hipSuccess)
-            e = hipMemcpyAsync(host_out, colour ? (void*)rc : (void*)rd, need, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(rc);
-        (void)hipFree(rd);
+            e = hipMemcpyAsync(host_out, colour ? (void*)rc : (void*)rd, need, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
         if (e != hipSuccess) return fail(c, -3, std::string("insitu_read: ") + hipGetErrorString(e));
         return 0;
     }
@@ -1791,25 +1831,20 @@ int insitu_read(insitu_ctx* c, int which, int slot, void* host_out, size_t cap) 
     case INSITU_BUF_RECEIVED_COLOR:
     case INSITU_BUF_RECEIVED_DEPTH: {   // block v = list v of the compositor (source-major)
         const size_t n = c->stripPx * (size_t)c->S;
-        float4* rc = nullptr;
-        float2* rd = nullptr;
-        HIPCHK(c, hipMalloc(&rc, n * sizeof(float4)));
-        if (hipMalloc(&rd, n * sizeof(float2)) != hipSuccess) {
-            (void)hipFree(rc);
-            return fail(c, -5, "insitu_read: scratch allocation failed");
-        }
+        DevBuf<float4> rc;
+        DevBuf<float2> rd;
+        HIPCHK(c, rc.try_alloc(n));
+        if (rd.try_alloc(n) != hipSuccess) return fail(c, -5, "insitu_read: scratch allocation failed");
         const bool colour = which == INSITU_BUF_RECEIVED_COLOR;
         const size_t blk = colour ? n * sizeof(float4) : n * sizeof(float2);
         hipError_t e = hipSuccess;
         for (int v = 0; v < c->V && e == hipSuccess; ++v) {
-            e = launch_vdi_list_to_reference(list_of(c, v), c->S, c->H, c->strip_w, c->strip_tiles, rc, rd, c->stream);
+            e = launch_vdi_list_to_reference(list_of(c, f, v), c->S, c->H, c->strip_w, c->strip_tiles, rc, rd, st);
             if (e == hipSuccess)
                 e = hipMemcpyAsync((uint8_t*)host_out + (size_t)v * blk, colour ? (void*)rc : (void*)rd, blk,
-                                   hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+                                   hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
         }
-        (void)hipFree(rc);
-        (void)hipFree(rd);
         if (e != hipSuccess) return fail(c, -3, std::string("insitu_read: ") + hipGetErrorString(e));
         return 0;
     }
@@ -1819,7 +1854,7 @@ int insitu_read(insitu_ctx* c, int which, int slot, void* host_out, size_t cap) 
 
 int insitu_read_region(insitu_ctx* c, int which, int slot, int x0, int x1, void* host_out, size_t cap) {
     if (!c) return fail(nullptr, -1, "insitu_read_region: null context");
-    StreamScope scope(c, read_stream(c));   // (a pipelined frame in flight: the completed frame's slot)
+    auto [f, st] = completed_frame(c);
     if (!host_out) return fail(c, -1, "insitu_read_region: null output");
     if (c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_read_region: VDI mode only");
     if (which != INSITU_BUF_VDI_COLOR && which != INSITU_BUF_VDI_DEPTH && which != INSITU_BUF_PASSES)
@@ -1830,34 +1865,27 @@ int insitu_read_region(insitu_ctx* c, int which, int slot, int x0, int x1, void*
     const size_t n = nx * (size_t)c->H * (size_t)c->S;
     const size_t need = which == INSITU_BUF_VDI_COLOR ? n * 16 : (which == INSITU_BUF_VDI_DEPTH ? n * 8 : nx * (size_t)c->H);
     if (cap < need) return fail(c, -1, "insitu_read_region: output buffer too small");
-    if (which == INSITU_BUF_PASSES && !c->cur->passes) return fail(c, -1, "insitu_read_region: context keeps no pass counts");
+    if (which == INSITU_BUF_PASSES && !f.passes) return fail(c, -1, "insitu_read_region: context keeps no pass counts");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (int rc = check_fault(c)) return rc;
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (int rc = check_fault(c, f)) return rc;
     if (which == INSITU_BUF_PASSES) {   // (H, x1-x0) rows of the (H, W) pass counts
-        HIPCHK(c, hipMemcpy2D(host_out, nx, c->cur->passes + (size_t)slot * (size_t)c->W * (size_t)c->H + (size_t)x0,
+        HIPCHK(c, hipMemcpy2D(host_out, nx, f.passes + (size_t)slot * (size_t)c->W * (size_t)c->H + (size_t)x0,
                               (size_t)c->W, nx, (size_t)c->H, hipMemcpyDeviceToHost));
         return 0;
     }
-    void* scratch = nullptr;
-    HIPCHK(c, hipMalloc(&scratch, n * (which == INSITU_BUF_VDI_COLOR ? 16 : 8)));
-    float4* rc_ = which == INSITU_BUF_VDI_COLOR ? (float4*)scratch : nullptr;
-    float* rd_ = which == INSITU_BUF_VDI_DEPTH ? (float*)scratch : nullptr;
-    hipError_t e = hipSuccess;
-    // the kernel writes both outputs: give the unused one a throwaway buffer
-    void* other = nullptr;
-    e = hipMalloc(&other, n * (which == INSITU_BUF_VDI_COLOR ? 8 : 16));
-    if (e == hipSuccess) {
-        if (!rc_) rc_ = (float4*)other;
-        else rd_ = (float*)other;
-        e = launch_vdi_to_reference(c->cur->vcol_send, c->cur->vdep_send, c->cur->seg_pending, (size_t)c->W * (size_t)c->H,
+    // the kernel writes both outputs: the one not asked for is a throwaway (both freed at scope exit)
+    DevBuf<float4> rc_;
+    DevBuf<float> rd_;
+    hipError_t e = rc_.try_alloc(n);
+    if (e == hipSuccess) e = rd_.try_alloc(n * 2);
+    if (e == hipSuccess)
+        e = launch_vdi_to_reference(f.vcol_send, f.vdep_send, f.seg_pending, (size_t)c->W * (size_t)c->H,
                                     (size_t)c->strip_w, (size_t)c->W, c->W, x0, (int)nx, c->H, c->S, c->strip_w,
-                                    c->strip_tiles, c->BV, slot, rc_, rd_, c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(host_out, scratch, need, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(scratch);
-    if (other) (void)hipFree(other);
+                                    c->strip_tiles, c->BV, slot, rc_, rd_, st);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(host_out, which == INSITU_BUF_VDI_COLOR ? (void*)rc_ : (void*)rd_, need, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(c, -3, std::string("insitu_read_region: ") + hipGetErrorString(e));
     return 0;
 }
@@ -1874,30 +1902,12 @@ int view_reserve(insitu_ctx* c, int W, int H, int S) {
     v.counted = false;
     const int tx = (W + 7) / 8, ty = (H + 7) / 8;
     const size_t px = (size_t)W * (size_t)H, entries = px * (size_t)S, tiles = (size_t)tx * (size_t)ty;
+    v.vdi = ViewVdi{};
     int rc = 0;
-    if (entries > v.cap_entries) {
-        if (v.vdi.col) (void)hipFree(v.vdi.col);
-        if (v.vdi.dep) (void)hipFree(v.vdi.dep);
-        v.vdi.col = nullptr;
-        v.vdi.dep = nullptr;
-        v.cap_entries = 0;
-        if ((rc = dev_alloc(c, &v.vdi.col, entries)) || (rc = dev_alloc(c, &v.vdi.dep, entries))) return rc;
-        v.cap_entries = entries;
-    }
-    if (px > v.cap_px) {
-        if (v.vdi.cnt) (void)hipFree(v.vdi.cnt);
-        v.vdi.cnt = nullptr;
-        v.cap_px = 0;
-        if ((rc = dev_alloc(c, &v.vdi.cnt, px))) return rc;
-        v.cap_px = px;
-    }
-    if (tiles > v.cap_tiles) {
-        if (v.vdi.tmax) (void)hipFree(v.vdi.tmax);
-        v.vdi.tmax = nullptr;
-        v.cap_tiles = 0;
-        if ((rc = dev_alloc(c, &v.vdi.tmax, tiles))) return rc;
-        v.cap_tiles = tiles;
-    }
+    if ((rc = v.col.reserve(c, entries)) || (rc = v.dep.reserve(c, entries)) || (rc = v.cnt.reserve(c, px)) ||
+        (rc = v.tmax.reserve(c, tiles)))
+        return rc;
+    v.vdi.col = v.col; v.vdi.dep = v.dep; v.vdi.cnt = v.cnt; v.vdi.tmax = v.tmax;
     v.vdi.W = W; v.vdi.H = H; v.vdi.S = S; v.vdi.tiles_x = tx; v.vdi.tiles_y = ty;
     return 0;
 }
@@ -1918,8 +1928,7 @@ int view_build(insitu_ctx* c, const ViewSource& src, const float* pv_g, const ch
 int insitu_view_bind(insitu_ctx* c, int source, int slot) {
     if (!c) return fail(nullptr, -1, "insitu_view_bind: null context");
     if (c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_view_bind: VDI mode only");
-    StreamScope scope(c, read_stream(c));   // (a pipelined frame in flight: the completed frame's slot)
-    const FrameSlot& f = *c->cur;
+    auto [f, st] = completed_frame(c);
     ViewSource src{};
     const float* pv = nullptr;
     int S = 0;
@@ -1947,9 +1956,9 @@ int insitu_view_bind(insitu_ctx* c, int source, int slot) {
     HIPCHK(c, hipSetDevice(c->cfg.device));
     // the frame's own work is done before the snapshot is taken (its render may still be running when no
     // stage after it has synchronised)
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(st));
     if (f.search_stream) HIPCHK(c, hipStreamSynchronize(f.search_stream));
-    if (int rc = check_fault(c)) return rc;
+    if (int rc = check_fault(c, f)) return rc;
     if (int rc = view_reserve(c, c->W, c->H, S)) return rc;
     return view_build(c, src, pv, "insitu_view_bind");
 }
@@ -1964,13 +1973,10 @@ int insitu_view_bind_host(insitu_ctx* c, const void* color, const void* depth, i
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (int rc = view_reserve(c, W, H, S)) return rc;
     const size_t n = (size_t)W * (size_t)H * (size_t)S;
-    float4* rc_ = nullptr;
-    float* rd_ = nullptr;
-    HIPCHK(c, hipMalloc(&rc_, n * sizeof(float4)));
-    if (hipMalloc(&rd_, n * 2 * sizeof(float)) != hipSuccess) {
-        (void)hipFree(rc_);
-        return fail(c, -5, "insitu_view_bind_host: staging allocation failed");
-    }
+    DevBuf<float4> rc_;   // (the staging pair is freed at scope exit: the view's stream is idle by then)
+    DevBuf<float> rd_;
+    HIPCHK(c, rc_.try_alloc(n));
+    if (rd_.try_alloc(n * 2) != hipSuccess) return fail(c, -5, "insitu_view_bind_host: staging allocation failed");
     hipError_t e = hipMemcpyAsync(rc_, color, n * sizeof(float4), hipMemcpyHostToDevice, c->view.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(rd_, depth, n * 2 * sizeof(float), hipMemcpyHostToDevice, c->view.stream);
     int rc = 0;
@@ -1983,8 +1989,6 @@ int insitu_view_bind_host(insitu_ctx* c, const void* color, const void* depth, i
         src.ref_dep = rd_;
         rc = view_build(c, src, pv, "insitu_view_bind_host");   // (blocks: the staging is free afterwards)
     }
-    (void)hipFree(rc_);
-    (void)hipFree(rd_);
     return rc;
 }
 
@@ -2000,17 +2004,9 @@ int pack_offsets(insitu_ctx* c, int check_E, unsigned long long expect_E, PackTo
     if (px > kPackMaxPixels) return fail(c, -1, std::string(who) + ": more than 2^30 pixels");
     const size_t blocks = (size_t)((px + (uint64_t)kPackBlockPx - 1) / (uint64_t)kPackBlockPx);
     int rc = 0;
-    if (!v.pk_totals && (rc = dev_alloc(c, &v.pk_totals, 1))) return rc;
-    if (!v.h_totals) HIPCHK(c, hipHostMalloc((void**)&v.h_totals, sizeof(PackTotals)));
-    if (blocks > v.pk_blocks) {
-        if (v.pk_bstat) (void)hipFree(v.pk_bstat);
-        if (v.pk_boff) (void)hipFree(v.pk_boff);
-        v.pk_bstat = nullptr;
-        v.pk_boff = nullptr;
-        v.pk_blocks = 0;
-        if ((rc = dev_alloc(c, &v.pk_bstat, blocks)) || (rc = dev_alloc(c, &v.pk_boff, blocks))) return rc;
-        v.pk_blocks = blocks;
-    }
+    if ((rc = v.pk_totals.reserve(c, 1)) || (rc = v.pk_bstat.reserve(c, blocks)) || (rc = v.pk_boff.reserve(c, blocks)))
+        return rc;
+    if (!v.h_totals) HIPCHK(c, v.h_totals.try_alloc(1));
     const PackOffsets o{v.vdi.cnt, v.pk_bstat, v.pk_boff, v.pk_totals, (uint32_t)px, (uint32_t)blocks};
     HIPCHK(c, hipEventRecord(v.ev0, v.stream));
     hipError_t e = launch_pack_offsets(o, v.vdi.S, check_E, expect_E, v.stream);
@@ -2041,15 +2037,7 @@ int pack_count_bound(insitu_ctx* c, float* ms, const char* who) {
 int pack_stage_reserve(insitu_ctx* c, const PackLayout& lay, size_t* colour_at) {
     ViewState& v = c->view;
     *colour_at = (lay.depth_bytes + 15) & ~(size_t)15;
-    const size_t need = *colour_at + lay.colour_bytes;
-    if (need > v.pk_stage_bytes) {
-        if (v.pk_stage) (void)hipFree(v.pk_stage);
-        v.pk_stage = nullptr;
-        v.pk_stage_bytes = 0;
-        if (int rc = dev_alloc(c, &v.pk_stage, need)) return rc;
-        v.pk_stage_bytes = need;
-    }
-    return 0;
+    return v.pk_stage.reserve(c, *colour_at + lay.colour_bytes);
 }
 
 bool pack_format_ok(int format) { return format == INSITU_PACK_FLOAT || format == INSITU_PACK_HALF; }
@@ -2096,7 +2084,7 @@ int insitu_view_pack(insitu_ctx* c, int format, void* host_out, size_t cap, size
     PackParams p{};
     p.vdi = v.vdi;
     p.boff = v.pk_boff;
-    p.dep = reinterpret_cast<float2*>(v.pk_stage);
+    p.dep = reinterpret_cast<float2*>(v.pk_stage.get());
     p.col = v.pk_stage + colour_at;
     p.half = format == INSITU_PACK_HALF ? 1 : 0;
     HIPCHK(c, hipEventRecord(v.ev0, v.stream));
@@ -2151,7 +2139,7 @@ int insitu_view_bind_packed(insitu_ctx* c, const void* data, size_t bytes) {
     PackParams p{};
     p.vdi = v.vdi;
     p.boff = v.pk_boff;
-    p.dep = reinterpret_cast<float2*>(v.pk_stage);
+    p.dep = reinterpret_cast<float2*>(v.pk_stage.get());
     p.col = v.pk_stage + colour_at;
     p.half = h.format == kPackHalf ? 1 : 0;
     HIPCHK(c, hipEventRecord(v.ev0, v.stream));
@@ -2188,16 +2176,10 @@ int insitu_view_render(insitu_ctx* c, const insitu_camera* cam, int out_w, int o
     mat4_mul_f(iv, ip, p.ipv_n);
     std::memcpy(p.pv_g, v.pv_g, sizeof p.pv_g);
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (px > v.out_cap) {
-        if (v.out_color) (void)hipFree(v.out_color);
-        if (v.out_image) (void)hipFree(v.out_image);
-        v.out_color = nullptr;
-        v.out_image = nullptr;
-        v.out_cap = 0;
-        v.out_w = v.out_h = 0;
+    if (px > v.out_color.count() || px > v.out_image.count()) {
+        v.out_w = v.out_h = 0;   // (nothing to read until this render is done)
         int rc = 0;
-        if ((rc = dev_alloc(c, &v.out_color, px)) || (rc = dev_alloc(c, &v.out_image, px))) return rc;
-        v.out_cap = px;
+        if ((rc = v.out_color.reserve(c, px)) || (rc = v.out_image.reserve(c, px))) return rc;
     }
     p.vdi = v.vdi;
     p.out_w = out_w; p.out_h = out_h;
@@ -2218,12 +2200,12 @@ int insitu_view_render(insitu_ctx* c, const insitu_camera* cam, int out_w, int o
 
 int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
     if (!c || !out) return fail(c, -1, "insitu_get_stats: null argument");
-    StreamScope scope(c, read_stream(c));   // (a pipelined frame in flight: the completed frame's slot)
+    const CompletedFrame done = completed_frame(c);
+    FrameSlot& f = done.f;
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    cache_observe(c);
+    HIPCHK(c, hipStreamSynchronize(done.s));
+    cache_observe(c, f);
     std::memset(out, 0, sizeof *out);
-    const FrameSlot& f = *c->cur;
     // the time from event a to event b of the slot's frame, when both were recorded
     auto span = [&f](int a, int b, float* ms) {
         return f.ev_valid[a] && f.ev_valid[b] && hipEventElapsedTime(ms, f.ev[a], f.ev[b]) == hipSuccess;
@@ -2280,12 +2262,12 @@ int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
 
 int insitu_pass_stats(insitu_ctx* c, double* mean_passes, long long* rays_hit) {
     if (!c || !mean_passes || !rays_hit) return fail(c, -1, "insitu_pass_stats: null argument");
-    StreamScope scope(c, read_stream(c));   // (a pipelined frame in flight: the completed frame's slot)
-    if (!c->cur->passes || c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_pass_stats: needs VDI mode + keep_passes");
+    auto [f, st] = completed_frame(c);
+    if (!f.passes || c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_pass_stats: needs VDI mode + keep_passes");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(st));
     std::vector<uint8_t> h((size_t)c->BV * (size_t)c->W * (size_t)c->H);
-    HIPCHK(c, hipMemcpy(h.data(), c->cur->passes, h.size(), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(h.data(), f.passes, h.size(), hipMemcpyDeviceToHost));
     long long hit = 0, sum = 0;
     for (uint8_t v : h)
         if (v) { ++hit; sum += v; }
@@ -2302,6 +2284,7 @@ int insitu_distribute_vdis(insitu_ctx* c, const void* subVDIColor, const void* s
     if (c->BV != 1) return fail(c, -1, "insitu_distribute_vdis: the host-buffer path carries one sub-VDI per rank");
     if (!c->camera_set) return fail(c, -1, "insitu_distribute_vdis: call insitu_set_camera (VDI metadata) first");
     HIPCHK(c, hipSetDevice(c->cfg.device));
+    FrameSlot& f = *c->cur;   // (an unpipelined stage of its own: the public exchange and composite follow it)
     if (c->mode == INSITU_MODE_PLAIN) {
         // rgba8 (dim0, dim1) colour + encoded depth; blocks of rows*dim0 texels (DistributedVolumeRenderer.kt:577)
         if (sizePerProcess != (long long)c->plainBlock * 4)
@@ -2309,7 +2292,7 @@ int insitu_distribute_vdis(insitu_ctx* c, const void* subVDIColor, const void* s
         const size_t bytes = (size_t)c->N * c->plainBlock * 4;
         HIPCHK(c, hipMemcpyAsync(c->d_pcol_send, subVDIColor, bytes, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_pdep_send, subVDIDepth, bytes, hipMemcpyHostToDevice, c->stream));
-        c->cur->rendered = true;
+        f.rendered = true;
         int rc = insitu_exchange(c);
         if (rc) return rc;
         for (int s = 0; s < c->N; ++s) {   // the received set, source-major (compositeVDIs' VDISetColour)
@@ -2329,11 +2312,9 @@ int insitu_distribute_vdis(insitu_ctx* c, const void* subVDIColor, const void* s
     if (sizePerProcess != (long long)(blkE * 4))
         return fail(c, -1, "insitu_distribute_vdis: VDI sizePerProcess must be H*W*S*4/commSize floats");
     const size_t allE = blkE * (size_t)c->N;
-    if (!c->d_ref_col) {
-        HIPCHK(c, hipMalloc(&c->d_ref_col, 2 * allE * sizeof(float4)));
-        HIPCHK(c, hipMalloc(&c->d_ref_dep, 2 * allE * 2 * sizeof(float)));
-        HIPCHK(c, hipMalloc(&c->d_ref_cnt, (size_t)c->N * c->stripPx * sizeof(uint16_t)));
-    }
+    if (int rc = c->d_ref_col.reserve(c, 2 * allE)) return rc;   // (allocated by the first call)
+    if (int rc = c->d_ref_dep.reserve(c, 2 * allE * 2)) return rc;
+    if (int rc = c->d_ref_cnt.reserve(c, (size_t)c->N * c->stripPx)) return rc;
     float4* send_c = c->d_ref_col;
     float4* recv_c = c->d_ref_col + allE;
     float* send_d = c->d_ref_dep;
@@ -2362,14 +2343,14 @@ int insitu_distribute_vdis(insitu_ctx* c, const void* subVDIColor, const void* s
     // uploadForCompositing (DistributedVolumes.kt:945-998): the received set feeds the compositor
     for (int s = 0; s < c->N; ++s) {
         const size_t slot = s == c->rank ? (size_t)c->rank * c->blockE : (size_t)s * c->blockE;
-        float4* dc = (s == c->rank ? c->cur->vcol_send : c->d_vcol_recv) + slot;
-        float2* dd = (s == c->rank ? c->cur->vdep_send : c->d_vdep_recv) + slot;
+        float4* dc = (s == c->rank ? f.vcol_send : c->d_vcol_recv) + slot;
+        float2* dd = (s == c->rank ? f.vdep_send : c->d_vdep_recv) + slot;
         HIPCHK(c, launch_vdi_from_reference(recv_c + (size_t)s * blkE, recv_d + (size_t)s * 2 * blkE, c->H, c->S,
                                             c->strip_w, c->strip_tiles, dc, dd, c->d_ref_cnt + (size_t)s * c->stripPx,
                                             c->stream));
     }
-    c->cur->rendered = true;
-    c->cur->exchanged = true;
+    f.rendered = true;
+    f.exchanged = true;
     c->lists_from_reference = true;
     int rc = insitu_composite(c);
     if (rc) return rc;

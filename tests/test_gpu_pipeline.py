@@ -10,6 +10,8 @@ it), under each trigger mode of INSITU_OPT_PIPE_TRIGGER.
 """
 from __future__ import annotations
 
+import copy
+
 import numpy as np
 import pytest
 import torch
@@ -125,6 +127,36 @@ def test_pipelined_frames_bit_exact(trigger):
     -- every frame's sub-VDIs, octree cells, pass counts and flattened image bit for bit."""
     with _ctx() as ctx:
         _run(ctx, trigger)
+
+
+@pytest.mark.parametrize("trigger", [1, 0, 2])
+def test_pipelined_rejected_call_leaves_pipeline_intact(trigger):
+    """A pipelined call the library rejects (a camera with nw = 0) between good frames, under each trigger: it
+    raises, completes nothing, and enqueues and counts nothing -- the next frame's first pass is gated on what
+    the frame in flight really stores to its slot's flag (trigger 1), so the frames after the rejected call
+    complete in order, each bit for bit the oracle's, and the flush leaves nothing in flight."""
+    a, b, _ = _scenes()
+    cams = _cams(3)
+    bad = copy.copy(cams[1])
+    bad.nw = np.float32(0.0)
+    with _ctx() as ctx:
+        ctx.set_option(native.OPT_PIPE_TRIGGER, trigger)
+        ctx.set_brick(0, a["vol"], a["model"])
+        ctx.set_brick(1, b["vol"], b["model"])
+        seen = []
+
+        def check(done, img):
+            _check_frame(ctx, _oracle_frame([a["vol"], b["vol"]], [a, b], cams[done]), cams[done], img)
+            seen.append(done)
+
+        assert ctx.frame_pipelined(cams[0], want_image=True)[0] == -1
+        with pytest.raises(RuntimeError, match="nw must be > 0"):
+            ctx.frame_pipelined(bad, want_image=True)
+        for cam in cams[1:]:
+            check(*ctx.frame_pipelined(cam, want_image=True))
+        check(*ctx.pipeline_flush(want_image=True))
+        assert seen == [0, 1, 2]
+        assert ctx.pipeline_flush()[0] == -1   # nothing in flight
 
 
 @pytest.mark.parametrize("oversub,depth", [(1, 0), (64, 0), (3, 1)])
