@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define INSITU_ABI_VERSION 10
+#define INSITU_ABI_VERSION 11
 #define INSITU_COMM_ID_BYTES 128
 
 typedef struct insitu_ctx insitu_ctx;
@@ -80,7 +80,9 @@ enum insitu_buf {
 /* What insitu_view_bind takes its VDI from. */
 enum insitu_view_source {
     INSITU_VIEW_GATHERED = 0, /* root of a composite_vdi context: the gathered composited VDI (W,H,S_out) */
-    INSITU_VIEW_BRICK = 1     /* brick `slot`'s sub-VDI (W,H,S)                                             */
+    INSITU_VIEW_BRICK = 1,    /* brick `slot`'s sub-VDI (W,H,S)                                             */
+    INSITU_VIEW_MERGED = 2    /* all sub-VDIs this rank rendered, merged per pixel by start depth (W,H,S_m);
+                                 `slot` must be 0                                   */
 };
 
 /* Colour precision of a packed VDI stream (insitu_view_pack); the depths are float32 in both. */
@@ -172,6 +174,11 @@ typedef struct insitu_stats {
     float ms_view;               /* GPU time of the last insitu_view_render's kernel (0 until one has run)  */
     float ms_pack;               /* GPU time of the kernels of the last insitu_view_pack or insitu_view_bind_packed
                                     (offsets, copy; the copies to and from the host are not in it)           */
+    int view_slots;              /* slots per pixel S of the bound VDI, whatever bound it (0: none bound)       */
+    long long view_overlaps;     /* merged binds: adjacent entries of the bound lists whose next start depth lies
+                                    before the previous end (bricks that overlap in space; the viewer trusts a
+                                    list not to); 0 for the binds of one VDI                                   */
+    float ms_view_bind;          /* GPU time of the kernels of the last bind (uploads and readbacks not in it)  */
 } insitu_stats;
 
 /* Tuning and diagnostics options (insitu_set_option); the defaults are the measured optimum. */
@@ -266,7 +273,12 @@ int insitu_read_region(insitu_ctx* ctx, int which, int slot, int x0, int x1, voi
  * insitu_frame_pipelined calls the completed frame, as insitu_read) with that frame's camera as the generating
  * camera, and blocks until the snapshot is built: later frames, pipelined ones included, do not disturb it.
  * INSITU_VIEW_GATHERED needs a composite_vdi context, rank 0 and a gathered frame; INSITU_VIEW_BRICK a rendered
- * frame and 0 <= slot < the context's sub-VDIs. */
+ * frame and 0 <= slot < the context's sub-VDIs.  INSITU_VIEW_MERGED (slot 0) binds all of the rank's sub-VDIs of
+ * that frame as one VDI: per pixel their lists merged by start depth, the lowest slot first on a tie, as the
+ * flatten compositor walks them (VDICompositor.comp:58-91), every entry copied bit for bit.  The bound VDI has
+ * S_m = max(1, the longest merged list) slots (insitu_stats.view_slots); more than 255 is rejected with -1 and
+ * leaves no VDI bound, as every failed merged bind does.  With one sub-VDI (one brick, merge_bricks) it is
+ * INSITU_VIEW_BRICK of slot 0; with nranks > 1 it merges the rank's own bricks only. */
 int insitu_view_bind(insitu_ctx* ctx, int source, int slot);
 /* The same from host memory: a VDI in the reference layout -- colour (W,H,S,4) rgba32f and depth (W,H,2S) r32f, x
  * slowest, as the dumps hold it (vdi_io.read_vdi) -- with the camera that generated it.  W, H and S (1..255) need
@@ -274,6 +286,11 @@ int insitu_view_bind(insitu_ctx* ctx, int source, int slot);
  * trusted to be ordered by depth and not to overlap, as the generator and the compositor write them. */
 int insitu_view_bind_host(insitu_ctx* ctx, const void* color, const void* depth, int W, int H, int S,
                           const insitu_camera* gen_cam);
+/* The merged bind from host memory: n (1..32) such VDIs of one W, H, S and one generating camera -- the per-rank
+ * dumps of a frame, say (DistributedVolumes.kt:848-849) -- merged as INSITU_VIEW_MERGED merges, colors[j] / depths[j]
+ * taking the place of slot j.  n = 1 is insitu_view_bind_host.  A failed call leaves no VDI bound. */
+int insitu_view_bind_host_set(insitu_ctx* ctx, const void* const* colors, const void* const* depths, int n, int W,
+                              int H, int S, const insitu_camera* gen_cam);
 /* Render the bound VDI from `cam` at out_w x out_h and block until it is done.  host_out non-NULL: receives the
  * (out_h,out_w) rgba8 image (cap >= out_w*out_h*4).  INSITU_BUF_VIEW_COLOR / INSITU_BUF_VIEW_IMAGE then hold the
  * rgba32f accumulator and the image (insitu_read, insitu_buffer_bytes).  Only cam's view and projection (and its

@@ -252,6 +252,11 @@ struct ViewState {
     PinnedBuf<PackTotals> h_totals;
     DevBuf<unsigned char> pk_stage;     // the depth and colour sections on the device, kept across calls
     float ms_pack = 0.0f;               // the last pack's or unpack's kernels
+    // the merged bind (INSITU_VIEW_MERGED, insitu_view_bind_host_set; vdi_view_merge.hip)
+    DevBuf<MergeTotals> mg_totals;      // device; read back through h_mg_totals (pinned)
+    PinnedBuf<MergeTotals> h_mg_totals;
+    long long overlaps = 0;             // of the bound VDI (0 for the single-VDI binds)
+    float ms_bind = 0.0f;               // the last bind's kernels
 };
 
 struct insitu_ctx {
@@ -1892,12 +1897,19 @@ int insitu_read_region(insitu_ctx* c, int which, int slot, int x0, int x1, void*
 
 namespace {
 
-// the view's stream and events (first bind), and room for a VDI of (W, H, S) in the view layout
-int view_reserve(insitu_ctx* c, int W, int H, int S) {
+// the view's stream and events (first bind)
+int view_stream(insitu_ctx* c) {
     ViewState& v = c->view;
     if (!v.stream) HIPCHK(c, hipStreamCreateWithFlags(&v.stream, hipStreamNonBlocking));
     if (!v.ev0) HIPCHK(c, hipEventCreate(&v.ev0));
     if (!v.ev1) HIPCHK(c, hipEventCreate(&v.ev1));
+    return 0;
+}
+
+// ... and room for a VDI of (W, H, S) in the view layout
+int view_reserve(insitu_ctx* c, int W, int H, int S) {
+    ViewState& v = c->view;
+    if (int rc = view_stream(c)) return rc;
     v.bound = false;
     v.counted = false;
     const int tx = (W + 7) / 8, ty = (H + 7) / 8;
@@ -1915,9 +1927,59 @@ int view_reserve(insitu_ctx* c, int W, int H, int S) {
 // view_build_kernel over `src` on the view's stream; blocks until the snapshot is built
 int view_build(insitu_ctx* c, const ViewSource& src, const float* pv_g, const char* who) {
     ViewState& v = c->view;
+    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
     hipError_t e = launch_view_build(src, v.vdi, v.stream);
+    if (e == hipSuccess) e = hipEventRecord(v.ev1, v.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
     if (e != hipSuccess) return fail(c, -3, std::string(who) + ": view_build_kernel: " + hipGetErrorString(e));
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_bind = ms;
+    std::memcpy(v.pv_g, pv_g, sizeof v.pv_g);
+    v.overlaps = 0;
+    v.bound = true;
+    return 0;
+}
+
+// After one of the two merge kernels' launches (e) on the view's stream, behind ev0: the totals on the host; blocks.
+// *ms = the kernel's HIP-event time.
+int view_merge_done(insitu_ctx* c, hipError_t e, const char* who, const char* kernel, MergeTotals* tot, float* ms) {
+    ViewState& v = c->view;
+    if (e != hipSuccess) return fail(c, -3, std::string(who) + ": " + kernel + ": " + hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(v.ev1, v.stream));
+    HIPCHK(c, hipMemcpyAsync(v.h_mg_totals, v.mg_totals, sizeof(MergeTotals), hipMemcpyDeviceToHost, v.stream));
+    HIPCHK(c, hipStreamSynchronize(v.stream));
+    *tot = *v.h_mg_totals;
+    *ms = 0.0f;
+    (void)hipEventElapsedTime(ms, v.ev0, v.ev1);
+    return 0;
+}
+
+// The merged bind: the src.n lists per pixel of a (W, H) window of S-slot lists, merged by start
+// depth into a VDI of S_m = max(1, the longest merged list) slots.  More than 255 is rejected and leaves no VDI
+// bound.  Blocks until the snapshot is built.
+int view_merge(insitu_ctx* c, const ViewSource& src, int W, int H, int S, const float* pv_g, const char* who) {
+    ViewState& v = c->view;
+    v.bound = false;
+    v.counted = false;
+    if (int rc = view_stream(c)) return rc;
+    if (int rc = v.mg_totals.reserve(c, 1)) return rc;
+    if (!v.h_mg_totals) HIPCHK(c, v.h_mg_totals.try_alloc(1));
+    MergeTotals tot{};
+    float ms_count = 0.0f, ms_merge = 0.0f;
+    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+    if (int rc = view_merge_done(c, launch_view_merge_count(src, W, H, S, v.mg_totals, v.stream), who,
+                                 "view_merge_count_kernel", &tot, &ms_count))
+        return rc;
+    if (tot.max_count > 255u)
+        return fail(c, -1, std::string(who) + ": the merged lists hold up to " + std::to_string(tot.max_count) +
+                               " entries per pixel, at most 255 can be bound");
+    if (int rc = view_reserve(c, W, H, tot.max_count > 0u ? (int)tot.max_count : 1)) return rc;
+    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+    if (int rc = view_merge_done(c, launch_view_merge(src, S, v.vdi, v.mg_totals, v.stream), who, "view_merge_kernel", &tot,
+                                 &ms_merge))
+        return rc;
+    v.ms_bind = ms_count + ms_merge;
+    v.overlaps = (long long)tot.overlaps;
     std::memcpy(v.pv_g, pv_g, sizeof v.pv_g);
     v.bound = true;
     return 0;
@@ -1927,9 +1989,14 @@ int view_build(insitu_ctx* c, const ViewSource& src, const float* pv_g, const ch
 
 int insitu_view_bind(insitu_ctx* c, int source, int slot) {
     if (!c) return fail(nullptr, -1, "insitu_view_bind: null context");
+    if (source == INSITU_VIEW_MERGED) {   // (a failed merged bind leaves no VDI bound)
+        c->view.bound = false;
+        c->view.counted = false;
+    }
     if (c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_view_bind: VDI mode only");
     auto [f, st] = completed_frame(c);
     ViewSource src{};
+    src.n = 1;
     const float* pv = nullptr;
     int S = 0;
     if (source == INSITU_VIEW_GATHERED) {
@@ -1941,12 +2008,15 @@ int insitu_view_bind(insitu_ctx* c, int source, int slot) {
         src.B = 1; src.b = 0;
         S = c->S_out;
         pv = c->gvdi_pv;
-    } else if (source == INSITU_VIEW_BRICK) {
+    } else if (source == INSITU_VIEW_BRICK || source == INSITU_VIEW_MERGED) {
+        if (source == INSITU_VIEW_MERGED && slot != 0)
+            return fail(c, -1, "insitu_view_bind: INSITU_VIEW_MERGED takes slot 0 (it binds every sub-VDI of the rank)");
         if (slot < 0 || slot >= c->BV) return fail(c, -1, "insitu_view_bind: slot out of range");
         if (!f.rendered || !f.ev_valid[EvRenderEnd]) return fail(c, -1, "insitu_view_bind: no frame rendered yet");
         src.col = f.vcol_send; src.dep = f.vdep_send; src.cnt = f.seg_pending;
         src.cnt_stride = (size_t)c->W * (size_t)c->H; src.cnt_dstride = (size_t)c->strip_w; src.cnt_pitch = (size_t)c->W;
         src.B = c->BV; src.b = slot;
+        if (source == INSITU_VIEW_MERGED) src.n = c->BV;   // slots 0..BV-1: the whole window
         S = c->S;
         pv = f.pv;
     } else {
@@ -1959,37 +2029,74 @@ int insitu_view_bind(insitu_ctx* c, int source, int slot) {
     HIPCHK(c, hipStreamSynchronize(st));
     if (f.search_stream) HIPCHK(c, hipStreamSynchronize(f.search_stream));
     if (int rc = check_fault(c, f)) return rc;
+    // (a set of one list is that list: bound with its own S slots, as INSITU_VIEW_BRICK binds it)
+    if (src.n > 1) return view_merge(c, src, c->W, c->H, S, pv, "insitu_view_bind");
     if (int rc = view_reserve(c, c->W, c->H, S)) return rc;
     return view_build(c, src, pv, "insitu_view_bind");
 }
+
+namespace {
+
+// n dense VDIs in the reference layout, staged on the device and bound: one as it is (view_build_kernel, S slots),
+// several merged (view_merge)
+int view_bind_host_lists(insitu_ctx* c, const char* who, const void* const* colors, const void* const* depths, int n,
+                         int W, int H, int S, const insitu_camera* gen_cam) {
+    if (W <= 0 || H <= 0 || S < 1 || S > 255) return fail(c, -1, std::string(who) + ": needs W, H > 0 and S in [1,255]");
+    float pv[16];
+    mat4_mul_f(gen_cam->proj, gen_cam->view, pv);
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (n == 1) {
+        if (int rc = view_reserve(c, W, H, S)) return rc;
+    } else if (int rc = view_stream(c)) {
+        return rc;
+    }
+    const size_t E = (size_t)W * (size_t)H * (size_t)S;
+    DevBuf<float4> rc_;   // (the staging pair is freed at scope exit: the view's stream is idle by then)
+    DevBuf<float2> rd_;
+    HIPCHK(c, rc_.try_alloc(E * (size_t)n));
+    if (rd_.try_alloc(E * (size_t)n) != hipSuccess) return fail(c, -5, std::string(who) + ": staging allocation failed");
+    hipError_t e = hipSuccess;
+    for (int j = 0; j < n && e == hipSuccess; ++j) {
+        e = hipMemcpyAsync(rc_ + E * (size_t)j, colors[j], E * sizeof(float4), hipMemcpyHostToDevice, c->view.stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(rd_ + E * (size_t)j, depths[j], E * sizeof(float2), hipMemcpyHostToDevice, c->view.stream);
+    }
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->view.stream);
+        return fail(c, -3, std::string(who) + ": upload: " + hipGetErrorString(e));
+    }
+    ViewSource src{};
+    src.col = rc_;
+    src.dep = rd_;
+    src.reference = 1;
+    src.ref_stride = E;
+    src.n = n;
+    // (both block: the staging is free afterwards)
+    if (n == 1) return view_build(c, src, pv, who);
+    return view_merge(c, src, W, H, S, pv, who);
+}
+
+}  // namespace
 
 int insitu_view_bind_host(insitu_ctx* c, const void* color, const void* depth, int W, int H, int S,
                           const insitu_camera* gen_cam) {
     if (!c) return fail(nullptr, -1, "insitu_view_bind_host: null context");
     if (!color || !depth || !gen_cam) return fail(c, -1, "insitu_view_bind_host: null argument");
-    if (W <= 0 || H <= 0 || S < 1 || S > 255) return fail(c, -1, "insitu_view_bind_host: needs W, H > 0 and S in [1,255]");
-    float pv[16];
-    mat4_mul_f(gen_cam->proj, gen_cam->view, pv);
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (int rc = view_reserve(c, W, H, S)) return rc;
-    const size_t n = (size_t)W * (size_t)H * (size_t)S;
-    DevBuf<float4> rc_;   // (the staging pair is freed at scope exit: the view's stream is idle by then)
-    DevBuf<float> rd_;
-    HIPCHK(c, rc_.try_alloc(n));
-    if (rd_.try_alloc(n * 2) != hipSuccess) return fail(c, -5, "insitu_view_bind_host: staging allocation failed");
-    hipError_t e = hipMemcpyAsync(rc_, color, n * sizeof(float4), hipMemcpyHostToDevice, c->view.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(rd_, depth, n * 2 * sizeof(float), hipMemcpyHostToDevice, c->view.stream);
-    int rc = 0;
-    if (e != hipSuccess) {
-        rc = fail(c, -3, std::string("insitu_view_bind_host: upload: ") + hipGetErrorString(e));
-        (void)hipStreamSynchronize(c->view.stream);
-    } else {
-        ViewSource src{};
-        src.ref_col = rc_;
-        src.ref_dep = rd_;
-        rc = view_build(c, src, pv, "insitu_view_bind_host");   // (blocks: the staging is free afterwards)
-    }
-    return rc;
+    return view_bind_host_lists(c, "insitu_view_bind_host", &color, &depth, 1, W, H, S, gen_cam);
+}
+
+int insitu_view_bind_host_set(insitu_ctx* c, const void* const* colors, const void* const* depths, int n, int W, int H,
+                              int S, const insitu_camera* gen_cam) {
+    const char* who = "insitu_view_bind_host_set";
+    if (!c) return fail(nullptr, -1, std::string(who) + ": null context");
+    c->view.bound = false;   // (a failed bind leaves no VDI bound)
+    c->view.counted = false;
+    if (!colors || !depths || !gen_cam) return fail(c, -1, std::string(who) + ": null argument");
+    if (n < 1 || n > kMaxLists)
+        return fail(c, -1, std::string(who) + ": " + std::to_string(n) + " VDIs, needs 1 to " + std::to_string(kMaxLists));
+    for (int j = 0; j < n; ++j)
+        if (!colors[j] || !depths[j]) return fail(c, -1, std::string(who) + ": null VDI " + std::to_string(j));
+    return view_bind_host_lists(c, who, colors, depths, n, W, H, S, gen_cam);
 }
 
 // ---- the packed stream of the bound VDI (vdi_pack.hip, vdi_pack_format.h) ----
@@ -2148,8 +2255,9 @@ int insitu_view_bind_packed(insitu_ctx* c, const void* data, size_t bytes) {
     HIPCHK(c, hipEventRecord(v.ev1, v.stream));
     HIPCHK(c, hipStreamSynchronize(v.stream));
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_pack = ms_count + ms;
+    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_pack = v.ms_bind = ms_count + ms;
     std::memcpy(v.pv_g, h.pv_g, sizeof v.pv_g);
+    v.overlaps = 0;
     v.pk_E = h.E;
     v.counted = true;
     v.bound = true;
@@ -2250,6 +2358,9 @@ int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
     (void)hipGetLastError();
     out->ms_view = c->view.ms;
     out->ms_pack = c->view.ms_pack;
+    out->view_slots = c->view.bound ? c->view.vdi.S : 0;
+    out->view_overlaps = c->view.bound ? c->view.overlaps : 0;
+    out->ms_view_bind = c->view.ms_bind;
     out->ms_sample = out->ms_render;
     float a = 0.0f, b = 0.0f;
     if (c->mode == INSITU_MODE_VDI && f.ev_valid[EvRenderEnd] && span(EvRenderStart, EvSampleEnd, &a) &&

@@ -286,21 +286,24 @@ struct ViewVdi {
     int W, H, S, tiles_x, tiles_y;
 };
 
-// What view_build_kernel reads.  Slotted (ref_col == null): the [d][b][xt][i][y][xx] blocks of the
-// generator's sub-VDIs and of the gathered composited VDI, entry of slot i of pixel (x, y) of brick b at
-// ((d*B + b)*strip_tiles*S*H*8) + ((xt*S + i)*H + y)*8 + xx with d = x / strip_w, xt = (x % strip_w) / 8,
-// and the pixel's stored count (& kPendingCount) at cnt[b*cnt_stride + d*cnt_dstride + y*cnt_pitch + x % strip_w]
-// (the parameters of launch_vdi_to_reference).  Reference layout (ref_col != null): colour (W,H,S) rgba32f and
-// depth (W,H,2S) r32f, x slowest, every slot present.  Either way a list ends before its first entry whose start
-// depth is 0 (determineNextSupseg never picks such a front).
+// What view_build_kernel and the merge kernels (vdi_view_merge.hip) read: n lists per pixel, list j of pixel (x, y)
+// with its entry k at col/dep[e0 + j*lstride + k*estride] (view_at, vdi_view_source.h).  Slotted (reference == 0):
+// the [d][b][xt][i][y][xx] blocks of the generator's sub-VDIs and of the gathered composited VDI, list j = brick
+// b + j, entry of slot i of pixel (x, y) of brick b at ((d*B + b)*strip_tiles*S*H*8) + ((xt*S + i)*H + y)*8 + xx
+// with d = x / strip_w, xt = (x % strip_w) / 8, and the pixel's stored count (& kPendingCount) at
+// cnt[b*cnt_stride + d*cnt_dstride + y*cnt_pitch + x % strip_w] (the parameters of launch_vdi_to_reference).
+// Reference layout (reference == 1): n staged VDIs ref_stride entries apart, each colour (W,H,S) rgba32f and depth
+// (W,H,S) {start, end} r32f pairs, x slowest, every slot present.  Either way a list ends before its first entry
+// whose start depth is 0 (determineNextSupseg never picks such a front).
 struct ViewSource {
     const float4* col;
     const float2* dep;
     const uint16_t* cnt;
     size_t cnt_stride, cnt_dstride, cnt_pitch;
     int strip_w, strip_tiles, B, b;
-    const float4* ref_col;
-    const float* ref_dep;
+    int reference;
+    size_t ref_stride;
+    int n;   // lists per pixel, 1..kMaxLists (view_build_kernel: 1)
 };
 
 struct ViewParams {
@@ -315,6 +318,18 @@ struct ViewParams {
 
 hipError_t launch_view_build(const ViewSource& src, const ViewVdi& dst, hipStream_t s);
 hipError_t launch_vdi_view(const ViewParams& p, hipStream_t s);
+
+// ---- the merged bind (vdi_view_merge.hip) ----
+struct MergeTotals {
+    uint32_t max_count;            // the longest merged list: the sum of the lists' lengths, largest over the pixels
+    uint32_t pad;
+    unsigned long long overlaps;   // adjacent merged entries whose next start lies before the previous end
+};
+// *tot zeroed on the stream, then max_count from the n lists of src over a W x H window of S-slot lists
+hipError_t launch_view_merge_count(const ViewSource& src, int W, int H, int S, MergeTotals* tot, hipStream_t s);
+// the k-way merge by start depth (lowest list on ties) of src's lists of S slots into dst (dst.S >= max_count):
+// dst's entries, counts and tile maxima, and tot->overlaps (zeroed on the stream first)
+hipError_t launch_view_merge(const ViewSource& src, int S, const ViewVdi& dst, MergeTotals* tot, hipStream_t s);
 
 // ---- the packed VDI stream (vdi_pack.hip, vdi_pack_format.h) ----
 constexpr int kPackBlockPx = 256;   // pixels per block of the offset passes and the copies: 4 waves x 64 pixels

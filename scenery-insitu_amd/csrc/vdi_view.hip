@@ -11,6 +11,7 @@
 // vdi_flatten_kernel blends.  tests/view_ref/view_ref.c restates it operation for operation.
 #include "insitu_device.h"
 #include "insitu_kernels.h"
+#include "vdi_view_source.h"
 
 #pragma clang fp contract(off)
 
@@ -26,27 +27,14 @@ __global__ __launch_bounds__(256) void view_build_kernel(const ViewSource P, con
     int n = 0;
     if (x < V.W && y < H) {
         const size_t o = ((size_t)y * (size_t)V.W + (size_t)x) * (size_t)S;
-        if (P.ref_col) {
-            const size_t r0 = ((size_t)x * (size_t)H + (size_t)y) * (size_t)S;
-            for (; n < S; ++n) {
-                const float2 se = make_float2(P.ref_dep[2 * (r0 + n)], P.ref_dep[2 * (r0 + n) + 1]);
-                if (se.x == 0.0f) break;
-                V.col[o + n] = P.ref_col[r0 + n];
-                V.dep[o + n] = se;
-            }
-        } else {
-            const int d = x / P.strip_w, xl = x - d * P.strip_w, xt = xl >> 3, xx = xl & 7;
-            const size_t blockE = (size_t)P.strip_tiles * (size_t)S * (size_t)H * 8;
-            const size_t e0 = ((size_t)d * (size_t)P.B + (size_t)P.b) * blockE + ((size_t)xt * (size_t)S * (size_t)H + (size_t)y) * 8 + (size_t)xx;
-            int stored = (int)(P.cnt[(size_t)P.b * P.cnt_stride + (size_t)d * P.cnt_dstride + (size_t)y * P.cnt_pitch + (size_t)xl] & kPendingCount);
-            stored = stored < S ? stored : S;   // (a corrupt count must not walk past the S slots)
-            for (; n < stored; ++n) {
-                const size_t e = e0 + (size_t)n * (size_t)H * 8;
-                const float2 se = P.dep[e];
-                if (se.x == 0.0f) break;
-                V.col[o + n] = P.col[e];
-                V.dep[o + n] = se;
-            }
+        const ViewAt at = view_at(P, x, y, H, S);
+        const int stored = view_slots(P, 0, x, y, S);
+        for (; n < stored; ++n) {
+            const size_t e = at.e0 + (size_t)n * at.estride;
+            const float2 se = P.dep[e];
+            if (se.x == 0.0f) break;
+            V.col[o + n] = P.col[e];
+            V.dep[o + n] = se;
         }
         V.cnt[(size_t)y * (size_t)V.W + (size_t)x] = (uint8_t)n;
     }

@@ -22,7 +22,7 @@ except Exception:  # pragma: no cover - torch is always present in this image
 PKG_ROOT = Path(__file__).resolve().parent.parent
 LIB_PATH = Path(os.environ.get("INSITU_HIP_LIB", PKG_ROOT / "lib" / "libinsitu_hip.so"))
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 COMM_ID_BYTES = 128
 
 MODE_PLAIN, MODE_VDI = 0, 1
@@ -33,7 +33,7 @@ BUF_PLAIN_COLOR, BUF_PLAIN_DEPTH, BUF_STRIP, BUF_IMAGE = 4, 5, 6, 7
 BUF_COMPOSITED_COLOR, BUF_COMPOSITED_DEPTH, BUF_GATHERED_COLOR, BUF_GATHERED_DEPTH, BUF_COMPOSITE_PASSES = 8, 9, 10, 11, 12
 BUF_RECEIVED_COLOR, BUF_RECEIVED_DEPTH = 13, 14
 BUF_VIEW_COLOR, BUF_VIEW_IMAGE = 15, 16
-VIEW_GATHERED, VIEW_BRICK = 0, 1   # enum insitu_view_source
+VIEW_GATHERED, VIEW_BRICK, VIEW_MERGED = 0, 1, 2   # enum insitu_view_source
 PACK_FLOAT, PACK_HALF = 0, 1       # enum insitu_pack_format
 
 # every symbol include/insitu_hip.h declares (tests check the .so exports all of them)
@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = (
     "insitu_get_stats", "insitu_pass_stats", "insitu_stream", "insitu_distribute_vdis", "insitu_gather_composited_vdis",
     "insitu_gather_composited_vdi_set", "insitu_local_group_create", "insitu_local_group_destroy",
     "insitu_set_option", "insitu_read_region", "insitu_frame_pipelined", "insitu_pipeline_flush",
-    "insitu_view_bind", "insitu_view_bind_host", "insitu_view_render",
+    "insitu_view_bind", "insitu_view_bind_host", "insitu_view_bind_host_set", "insitu_view_render",
     "insitu_view_pack_bytes", "insitu_view_pack", "insitu_view_bind_packed",
 )
 
@@ -87,6 +87,7 @@ class Stats(ctypes.Structure):
         ("cache_demand_bytes", ctypes.c_longlong), ("search_regroups", ctypes.c_int),
         ("ms_image_d2h", ctypes.c_float), ("ms_latency", ctypes.c_float), ("pipelined", ctypes.c_int),
         ("ms_ingest", ctypes.c_float), ("ms_view", ctypes.c_float), ("ms_pack", ctypes.c_float),
+        ("view_slots", ctypes.c_int), ("view_overlaps", ctypes.c_longlong), ("ms_view_bind", ctypes.c_float),
     ]
 
 
@@ -135,6 +136,7 @@ def load() -> ctypes.CDLL:
         "insitu_pipeline_flush": (i, [vp, vp, sz, ctypes.POINTER(ll)]),
         "insitu_view_bind": (i, [vp, i, i]),
         "insitu_view_bind_host": (i, [vp, vp, vp, i, i, i, ctypes.POINTER(Camera)]),
+        "insitu_view_bind_host_set": (i, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), i, i, i, i, ctypes.POINTER(Camera)]),
         "insitu_view_render": (i, [vp, ctypes.POINTER(Camera), i, i, vp, sz]),
         "insitu_view_pack_bytes": (sz, [vp, i]),
         "insitu_view_pack": (i, [vp, i, vp, sz, ctypes.POINTER(sz)]),

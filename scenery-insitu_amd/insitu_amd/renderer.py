@@ -252,8 +252,30 @@ class InSituContext:
     # ---------------------------------------------------------------- novel views of a VDI
     def view_bind(self, source: int = native.VIEW_BRICK, slot: int = 0):
         """Snapshot a VDI of the last completed frame for view_render: native.VIEW_GATHERED (root of a
-        composite_vdi context) or native.VIEW_BRICK (brick `slot`'s sub-VDI); its camera is that frame's."""
+        composite_vdi context), native.VIEW_BRICK (brick `slot`'s sub-VDI) or native.VIEW_MERGED (all of the
+        rank's sub-VDIs merged per pixel, slot 0; stats()["view_slots"] and ["view_overlaps"] describe it); its
+        camera is that frame's."""
         self._check(self.lib.insitu_view_bind(self.h, int(source), int(slot)), "insitu_view_bind")
+
+    def view_bind_host_set(self, colors, depths, gen_cam: scene.CameraSpec):
+        """Bind the per-pixel merge of several VDIs in the reference layout (sequences of colour (W,H,S,4) and
+        depth (W,H,2S) float32 arrays of one shape, vdi_io.merge_vdis on the GPU) with the camera that generated
+        them all."""
+        cs = [np.ascontiguousarray(c, dtype=np.float32) for c in colors]
+        ds = [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
+        if len(cs) != len(ds):
+            raise ValueError(f"view_bind_host_set: {len(cs)} colours, {len(ds)} depths")
+        for c, d in zip(cs, ds):
+            if c.ndim != 4 or c.shape[3] != 4 or c.shape != cs[0].shape or d.shape != (c.shape[0], c.shape[1], 2 * c.shape[2]):
+                raise ValueError(f"view_bind_host_set: colour {c.shape} / depth {d.shape} are not (W,H,S,4) / (W,H,2S) "
+                                 "of one size")
+        cam = gen_cam.native()
+        n = len(cs)
+        cp = (ctypes.c_void_p * max(n, 1))(*[c.ctypes.data for c in cs])
+        dp = (ctypes.c_void_p * max(n, 1))(*[d.ctypes.data for d in ds])
+        W, H, S = cs[0].shape[:3] if n else (0, 0, 0)
+        self._check(self.lib.insitu_view_bind_host_set(self.h, cp, dp, n, W, H, S, ctypes.byref(cam)),
+                    "insitu_view_bind_host_set")
 
     def view_bind_host(self, color: np.ndarray, depth: np.ndarray, gen_cam: scene.CameraSpec):
         """Bind a VDI in the reference layout -- colour (W,H,S,4), depth (W,H,2S) float32, as vdi_io.read_vdi

@@ -28,6 +28,10 @@ project's own format, what stands in for the compacted VDI the reference streams
 (VolumeFromFileExample.kt:907-1030): a 128-byte header, a count per pixel, and the stored entries alone.  The
 functions here are pure numpy on the reference layout, byte for byte what `InSituContext.view_pack` produces on the
 GPU, so a client without a GPU or this library's native half can read a stream.
+
+`merge_vdis` is the merged bind in numpy: the VDIs of one frame and camera -- the per-rank
+SubVDI dumps, say -- combined per pixel into one lossless VDI, as `InSituContext.view_bind_host_set` combines them on
+the GPU.
 """
 from __future__ import annotations
 
@@ -146,6 +150,60 @@ def write_metadata(base_path: str | Path, dataset: str, width: int, height: int,
 
 def read_metadata(path: str | Path) -> dict:
     return json.loads(Path(path).read_text())
+
+
+# ---------------------------------------------------------------- the merged VDI of a set
+MERGE_MAX_LISTS = 32     # kMaxLists
+MERGE_MAX_SLOTS = 255    # counts are bytes
+
+
+def merge_vdis(colours, depths) -> tuple[np.ndarray, np.ndarray, int]:
+    """Reference-layout VDIs of one size and one generating camera (sequences of colour (W, H, S, 4) and depth
+    (W, H, 2S) float32) -> (colour (W, H, S_m, 4), depth (W, H, 2 S_m), overlaps): per pixel the k-way merge of
+    the lists by start depth that the flatten compositor walks (determineNextSupseg, VDICompositor.comp:58-91).
+    A list ends before its first entry whose start depth is 0; the merged list takes, repeatedly, the front with
+    the smallest start depth below 100000, the lowest list on a tie; entries are copied bit for bit.  S_m =
+    max(1, the largest sum of a pixel's list lengths); ValueError when it exceeds 255.  overlaps counts the
+    adjacent merged entries whose next start lies before the previous end (0 for the bricks of a domain
+    decomposition; the novel-view renderer trusts a list not to overlap)."""
+    cs = [np.ascontiguousarray(c, dtype=np.float32) for c in colours]
+    ds = [np.ascontiguousarray(d, dtype=np.float32) for d in depths]
+    n = len(cs)
+    if not 1 <= n <= MERGE_MAX_LISTS or len(ds) != n:
+        raise ValueError(f"expected 1 to {MERGE_MAX_LISTS} colour / depth pairs")
+    W, H, S = cs[0].shape[:3] if cs[0].ndim == 4 else (0, 0, 0)
+    for c, d in zip(cs, ds):
+        if c.ndim != 4 or c.shape != (W, H, S, 4) or d.shape != (W, H, 2 * S) or min(W, H, S) < 1:
+            raise ValueError("expected colour (W, H, S, 4) and depth (W, H, 2S) float32 of one size")
+    col = np.stack(cs)                              # (n, W, H, S, 4)
+    dep = np.stack(ds).reshape(n, W, H, S, 2)
+    start = dep[..., 0]
+    lens = np.cumprod(start != 0.0, axis=3).sum(axis=3)      # (n, W, H)
+    s_m = max(1, int(lens.sum(axis=0).max()))
+    if s_m > MERGE_MAX_SLOTS:
+        raise ValueError(f"the merged lists hold up to {s_m} entries per pixel, at most {MERGE_MAX_SLOTS} fit")
+    out_col = np.zeros((W, H, s_m, 4), np.float32)
+    out_dep = np.zeros((W, H, s_m, 2), np.float32)
+    taken = np.zeros((n, W, H), np.intp)
+    wi, hi = np.indices((W, H))
+    overlaps, prev_end = 0, None
+    for k in range(s_m):
+        at = np.minimum(taken, S - 1)
+        front = np.take_along_axis(start, at[..., None], axis=3)[..., 0]
+        ok = (taken < lens) & (front < np.float32(100000.0))
+        j = np.argmin(np.where(ok, front, np.inf), axis=0)   # (the first of equal minima: the lowest list)
+        has = np.take_along_axis(ok, j[None], axis=0)[0]
+        if not has.any():
+            break
+        e = at[j, wi, hi]
+        d = dep[j, wi, hi, e]
+        out_col[has, k] = col[j, wi, hi, e][has]
+        out_dep[has, k] = d[has]
+        if k:
+            overlaps += int(np.count_nonzero(has & (d[..., 0] < prev_end)))
+        prev_end = d[..., 1]
+        taken[j[has], wi[has], hi[has]] += 1
+    return out_col, out_dep.reshape(W, H, 2 * s_m), overlaps
 
 
 # ---------------------------------------------------------------- the packed stream, format version 1

@@ -16,7 +16,15 @@ back (insitu_view_bind_packed): the stream sizes, the kernels' HIP-event time of
 (insitu_stats.ms_pack) and the wall time of insitu_view_pack with its copy to the host, one warm-up and then the
 best of three each, go into the JSON under "pack", beside the size of the dense readback they replace.
 
+--merged: the whole scene without the compositor's loss.  Config 2 in the default (flatten)
+context, all eight sub-VDIs bound with INSITU_VIEW_MERGED: the slots S_m, the stored entries, the overlap count, the
+bind's kernels (insitu_stats.ms_view_bind, best of three binds), the FLOAT and HALF packed sizes, and ms per view over
+the same orbit (skip on).  Then, in the same process, the same bricks in a composite_vdi context and the orbit over its
+gathered VDI; per camera the largest and the mean absolute difference of the two rgba8 images, in LSB -- what the
+VDICompositor's re-supersegmentation to S_out entries costs a novel view.  Prints one JSON line and nothing else runs.
+
 usage: python tools/view_bench.py [--brick 512] [--sim-n 512] [--views 36] [--passes 3] [--count-views 2] [--pack]
+       python tools/view_bench.py --merged [--brick 512] [--sim-n 512] [--views 36] [--passes 2]
 """
 from __future__ import annotations
 
@@ -43,6 +51,92 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def run_merged(args):
+    from insitu_amd import native, scene
+    from insitu_amd.renderer import InSituContext
+    from insitu_amd.vdi_io import PACK_HEADER_BYTES
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n = args.brick
+    bricks = scene.grid_bricks(n * 2, 2)
+    t0 = time.perf_counter()
+    flat = InSituContext(W_IMG, H_IMG, max_supersegments=S, bricks_per_rank=len(bricks), keep_passes=False)
+    comp = InSituContext(W_IMG, H_IMG, max_supersegments=S, bricks_per_rank=len(bricks), composite_vdi=True,
+                         max_output_supersegments=S, keep_passes=False)
+    for ctx in (flat, comp):
+        ctx.set_transfer(scene.transfer_function(), scene.colormap_hot(), conv_scale=1.0 / 0.5, conv_offset=0.0)
+    for bid, (origin, vw, _) in enumerate(bricks):
+        v = scene.gray_scott(n, steps=1500, seed=1000 + bid, device=dev, sim_n=min(args.sim_n, n)).contiguous()
+        for ctx in (flat, comp):
+            ctx.set_brick(bid, v, scene.brick_model(origin, vw), dtype=native.F32)
+        del v
+    vw = bricks[0][1]
+    torch.cuda.synchronize()
+    log(f"view_bench: {len(bricks)} bricks of {n}^3 in two contexts in {time.perf_counter() - t0:.1f} s")
+    cams = [scene.orbit_camera(W_IMG, H_IMG, yaw_deg=30.0 + 360.0 / args.views * i, pitch_deg=20.0, voxel_world=vw)
+            for i in range(args.views)]
+    ow, oh = args.out_w, args.out_h
+
+    def orbit(ctx):
+        """(best ms per camera over the timed passes after one warm-up pass, the images)"""
+        ms, imgs = [], None
+        for k in range(args.passes + 1):
+            row, imgs = [], []
+            for cam in cams:
+                imgs.append(ctx.view_render(cam, ow, oh))
+                row.append(ctx.stats()["ms_view"])
+            if k:
+                ms.append(row)
+        return np.asarray(ms).min(axis=0), imgs
+
+    flat.frame(cams[0])
+    ms_bind, wall_bind = [], []
+    for _ in range(4):   # one warm-up (it allocates), then the best of three
+        t0 = time.perf_counter()
+        flat.view_bind(native.VIEW_MERGED)
+        wall_bind.append((time.perf_counter() - t0) * 1e3)
+        ms_bind.append(flat.stats()["ms_view_bind"])
+    st = flat.stats()
+    px16 = (W_IMG * H_IMG + 15) // 16 * 16
+    sizes = {name: int(flat.lib.insitu_view_pack_bytes(flat.h, fmt))
+             for name, fmt in (("float", native.PACK_FLOAT), ("half", native.PACK_HALF))}
+    entries = (sizes["float"] - PACK_HEADER_BYTES - px16) // ENTRY_BYTES
+    merged = {"view_slots": int(st["view_slots"]), "entries": int(entries), "view_overlaps": int(st["view_overlaps"]),
+              "ms_view_bind": min(ms_bind[1:]), "ms_view_bind_first": ms_bind[0], "ms_bind_wall": min(wall_bind[1:]),
+              "packed_bytes": sizes, "view_layout_bytes": int(st["view_slots"]) * W_IMG * H_IMG * ENTRY_BYTES,
+              "slots_if_sized_by_n_times_S": len(bricks) * S}
+    log(f"view_bench: merged bind {json.dumps(merged)}")
+    ms_m, img_m = orbit(flat)
+    flat.close()
+
+    comp.frame(cams[0])
+    comp.view_bind(native.VIEW_GATHERED)
+    g_entries = (int(comp.lib.insitu_view_pack_bytes(comp.h, native.PACK_FLOAT)) - PACK_HEADER_BYTES - px16) // ENTRY_BYTES
+    ms_g, img_g = orbit(comp)
+    comp.close()
+    lsb_max, lsb_mean = [], []
+    for a, b in zip(img_m, img_g):
+        d = np.abs(a.astype(np.int16) - b.astype(np.int16))
+        lsb_max.append(int(d.max()))
+        lsb_mean.append(round(float(d.mean()), 4))
+    res = {
+        "metric": f"INSITU_VIEW_MERGED against INSITU_VIEW_GATHERED, novel views @{ow}x{oh} of config 2 "
+                  f"({W_IMG}x{H_IMG}, S = S_out = {S}, 8x{n}^3 volume)",
+        "views": args.views, "passes": args.passes,
+        "merged": merged, "gathered": {"view_slots": S, "entries": int(g_entries)},
+        "ms_per_view": {"merged": float(ms_m.mean()), "gathered": float(ms_g.mean())},
+        "ms_min_max": {"merged": [float(ms_m.min()), float(ms_m.max())], "gathered": [float(ms_g.min()), float(ms_g.max())]},
+        "ms_by_view_merged": [round(float(v), 4) for v in ms_m],
+        "ms_by_view_gathered": [round(float(v), 4) for v in ms_g],
+        "lsb_max_by_view": lsb_max, "lsb_mean_by_view": lsb_mean,
+        "lsb_max": max(lsb_max), "lsb_mean": float(np.mean(lsb_mean)),
+        "timing": "HIP events around the kernels (insitu_stats.ms_view, ms_view_bind), best of the passes per camera, "
+                  "skip on",
+    }
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--brick", type=int, default=512)
@@ -55,9 +149,13 @@ def main():
     ap.add_argument("--out-w", type=int, default=W_IMG)
     ap.add_argument("--out-h", type=int, default=H_IMG)
     ap.add_argument("--pack", action="store_true", help="also time the packed stream of the bound VDI, both formats")
+    ap.add_argument("--merged", action="store_true",
+                    help="INSITU_VIEW_MERGED of the flatten context against INSITU_VIEW_GATHERED of the composite_vdi one")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("view_bench: needs a GPU (timings are HIP-event times of the kernel)")
+    if args.merged:
+        return run_merged(args)
     from insitu_amd import native, scene
     from insitu_amd.renderer import InSituContext
 
