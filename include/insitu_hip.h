@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define INSITU_ABI_VERSION 11
+#define INSITU_ABI_VERSION 12
 #define INSITU_COMM_ID_BYTES 128
 
 typedef struct insitu_ctx insitu_ctx;
@@ -179,6 +179,13 @@ typedef struct insitu_stats {
                                     before the previous end (bricks that overlap in space; the viewer trusts a
                                     list not to); 0 for the binds of one VDI                                   */
     float ms_view_bind;          /* GPU time of the kernels of the last bind (uploads and readbacks not in it)  */
+    long long view_entries;      /* stored entries E of the bound VDI, the sum of its counts, whatever bound it and in
+                                    either layout (0: none bound)                                                */
+    long long view_bytes;        /* device bytes the bound VDI's view layout uses (not what the grow-only buffers
+                                    hold), tiles = ceil(W/8)*ceil(H/8), nblocks = ceil(W*H/256):
+                                      dense:   24*W*H*S + W*H + tiles
+                                      compact: 24*max(E,1) + 3*W*H + 8*nblocks + tiles                           */
+    int view_compact;            /* 1: the bound VDI is in the compact layout (INSITU_OPT_VIEW_COMPACT at its bind) */
 } insitu_stats;
 
 /* Tuning and diagnostics options (insitu_set_option); the defaults are the measured optimum. */
@@ -209,9 +216,14 @@ enum insitu_option {
                                       search, which then keeps one to two blocks per CU and leaves the other
                                       wave slots to the next frame's first pass (default 2048; 0 = the full
                                       persistent grid, as unpipelined frames)                              */
-    INSITU_OPT_VIEW_SKIP = 14      /* insitu_view_render: 1 (default): an 8x8 tile of lists whose largest count
+    INSITU_OPT_VIEW_SKIP = 14,     /* insitu_view_render: 1 (default): an 8x8 tile of lists whose largest count
                                       is 0 is stepped over in one step; 0: every cell is walked -- identical
                                       results                                                */
+    INSITU_OPT_VIEW_COMPACT = 15   /* the view layout of the VDIs bound from now on (every insitu_view_bind* call):
+                                      0 (default): dense, S slots per pixel; 1: compact, the stored entries alone
+                                      behind a 3-byte index per pixel -- the same renders and packed streams bit
+                                      for bit, less memory.  Takes effect at the next bind: a bound
+                                      VDI keeps its layout (insitu_stats.view_compact)                            */
 };
 
 int insitu_abi_version(void);
@@ -320,7 +332,7 @@ int insitu_view_bind_packed(insitu_ctx* ctx, const void* data, size_t bytes);
 int insitu_get_stats(insitu_ctx* ctx, insitu_stats* out);
 /* Set a tuning option (enum insitu_option) for the following renders; -1 on an unknown option or
  * a value out of range.  Environment variables INSITU_<OPTION NAME> (INSITU_EXACT_SEARCH,
- * INSITU_SEARCH_DEPTH, ..., INSITU_VIEW_SKIP) seed the values when the context is created (tuning scripts). */
+ * INSITU_SEARCH_DEPTH, ..., INSITU_VIEW_SKIP, INSITU_VIEW_COMPACT) seed the values when the context is created (tuning scripts). */
 int insitu_set_option(insitu_ctx* ctx, int option, long long value);
 /* Mean raymarch passes over rays that hit a brick, and the number of such rays, of the last
  * render over all local bricks (needs keep_passes; reads the pass buffer back). */

@@ -11,6 +11,7 @@
 #include "insitu_hip.h"
 #include "insitu_kernels.h"
 #include "vdi_pack_format.h"
+#include "vdi_view_layout.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -243,6 +244,9 @@ struct ViewState {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float ms = 0.0f;                    // the last render's kernel
     long long skip = 1;                 // INSITU_OPT_VIEW_SKIP
+    // the compact view layout: vdi.loc != null says the bound VDI has it
+    long long compact_next = 0;         // INSITU_OPT_VIEW_COMPACT: the layout the next bind takes
+    DevBuf<uint16_t> loc;               // a pixel's entries before it in its block (vdi.boff is pk_boff)
     // the packed stream of the bound VDI (insitu_view_pack, insitu_view_bind_packed; vdi_pack.hip)
     bool counted = false;               // pk_boff and pk_E describe the bound VDI (once per bind; view_reserve clears it)
     unsigned long long pk_E = 0;        // its stored entries
@@ -794,7 +798,7 @@ int insitu_create(const insitu_config* cfg, insitu_ctx** out) {
             {"INSITU_SUPER_TILE", INSITU_OPT_SUPER_TILE}, {"INSITU_REGROUP", INSITU_OPT_REGROUP},
             {"INSITU_EXACT_TILE_KEYS", INSITU_OPT_EXACT_TILE_KEYS}, {"INSITU_PIPE_TRIGGER", INSITU_OPT_PIPE_TRIGGER},
             {"INSITU_PIPE_OVERSUB", INSITU_OPT_PIPE_OVERSUB}, {"INSITU_PIPE_SEARCH_RAYS", INSITU_OPT_PIPE_SEARCH_RAYS},
-            {"INSITU_VIEW_SKIP", INSITU_OPT_VIEW_SKIP}};
+            {"INSITU_VIEW_SKIP", INSITU_OPT_VIEW_SKIP}, {"INSITU_VIEW_COMPACT", INSITU_OPT_VIEW_COMPACT}};
         for (const auto& nm : names) {
             if (const char* v = std::getenv(nm.name)) {
                 if (insitu_set_option(c, nm.opt, std::atoll(v)) != 0) {
@@ -866,6 +870,10 @@ int insitu_set_option(insitu_ctx* c, int option, long long v) {
     case INSITU_OPT_VIEW_SKIP:
         if (v != 0 && v != 1) break;
         c->view.skip = v;
+        return 0;
+    case INSITU_OPT_VIEW_COMPACT:   // (the next bind's layout; the bound VDI keeps its own)
+        if (v != 0 && v != 1) break;
+        c->view.compact_next = v;
         return 0;
     default:
         return fail(c, -1, "insitu_set_option: unknown option " + std::to_string(option));
@@ -1906,34 +1914,78 @@ int view_stream(insitu_ctx* c) {
     return 0;
 }
 
-// ... and room for a VDI of (W, H, S) in the view layout
+// room for `entries` list entries of the VDI being bound
+int view_reserve_entries(insitu_ctx* c, size_t entries) {
+    ViewState& v = c->view;
+    int rc = 0;
+    if ((rc = v.col.reserve(c, entries)) || (rc = v.dep.reserve(c, entries))) return rc;
+    v.vdi.col = v.col; v.vdi.dep = v.dep;
+    return 0;
+}
+
+// ... and room for a VDI of (W, H, S) in the view layout this bind takes (INSITU_OPT_VIEW_COMPACT as it stands now;
+// the bound VDI keeps it).  Dense: everything.  Compact: the counts, the tile maxima and the offsets; the entries
+// are reserved once the counts are there and add up to E (view_compact_offsets).
 int view_reserve(insitu_ctx* c, int W, int H, int S) {
     ViewState& v = c->view;
     if (int rc = view_stream(c)) return rc;
     v.bound = false;
     v.counted = false;
-    const int tx = (W + 7) / 8, ty = (H + 7) / 8;
-    const size_t px = (size_t)W * (size_t)H, entries = px * (size_t)S, tiles = (size_t)tx * (size_t)ty;
     v.vdi = ViewVdi{};
+    const bool compact = v.compact_next != 0;
+    ViewLayoutSize sz{};
+    if (compact ? !view_compact_size(W, H, S, 0, &sz) : !view_dense_size(W, H, S, &sz))
+        return fail(c, -1, "view bind: needs W, H > 0, at most 2^30 pixels and S in [1,255]");
     int rc = 0;
-    if ((rc = v.col.reserve(c, entries)) || (rc = v.dep.reserve(c, entries)) || (rc = v.cnt.reserve(c, px)) ||
-        (rc = v.tmax.reserve(c, tiles)))
-        return rc;
-    v.vdi.col = v.col; v.vdi.dep = v.dep; v.vdi.cnt = v.cnt; v.vdi.tmax = v.tmax;
-    v.vdi.W = W; v.vdi.H = H; v.vdi.S = S; v.vdi.tiles_x = tx; v.vdi.tiles_y = ty;
-    return 0;
+    if ((rc = v.cnt.reserve(c, (size_t)sz.px)) || (rc = v.tmax.reserve(c, (size_t)sz.tiles))) return rc;
+    if (compact) {
+        if ((rc = v.loc.reserve(c, (size_t)sz.px)) || (rc = v.pk_totals.reserve(c, 1)) ||
+            (rc = v.pk_bstat.reserve(c, (size_t)sz.nblocks)) || (rc = v.pk_boff.reserve(c, (size_t)sz.nblocks)))
+            return rc;
+        v.vdi.loc = v.loc; v.vdi.boff = v.pk_boff;
+    }
+    v.vdi.cnt = v.cnt; v.vdi.tmax = v.tmax;
+    v.vdi.W = W; v.vdi.H = H; v.vdi.S = S; v.vdi.tiles_x = (W + 7) / 8; v.vdi.tiles_y = (H + 7) / 8;
+    return compact ? 0 : view_reserve_entries(c, (size_t)sz.entries);
 }
 
-// view_build_kernel over `src` on the view's stream; blocks until the snapshot is built
+int pack_offsets(insitu_ctx* c, int check_E, unsigned long long expect_E, PackTotals* tot, float* ms, const char* who,
+                 bool timing_open = false);
+
+// The compact layout once its counts are on the device (after ev0 on the view's stream, which is what *ms counts
+// from): the offset passes -- boff, loc and E -- and room for the E entries (at least 1).  Blocks.  With check_E
+// the counts are a stream's: *tot tells the caller when they are to be rejected, and nothing is reserved then.
+int view_compact_offsets(insitu_ctx* c, int check_E, unsigned long long expect_E, PackTotals* tot, float* ms, const char* who) {
+    ViewState& v = c->view;
+    if (int rc = pack_offsets(c, check_E, expect_E, tot, ms, who, true)) return rc;
+    if (tot->bad) return check_E ? 0 : fail(c, -6, std::string(who) + ": a count of the VDI exceeds S (internal error)");
+    v.pk_E = tot->E;
+    v.counted = true;
+    return view_reserve_entries(c, tot->E > 0 ? (size_t)tot->E : 1);
+}
+
+// view_build_kernel over `src` on the view's stream (compact: the count pass, the offsets, the write pass); blocks
+// until the snapshot is built
 int view_build(insitu_ctx* c, const ViewSource& src, const float* pv_g, const char* who) {
     ViewState& v = c->view;
+    float ms_index = 0.0f;
     HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-    hipError_t e = launch_view_build(src, v.vdi, v.stream);
+    hipError_t e = hipSuccess;
+    if (v.vdi.loc) {
+        e = launch_view_build_count(src, v.vdi, v.stream);
+        if (e != hipSuccess) return fail(c, -3, std::string(who) + ": view_build_count_kernel: " + hipGetErrorString(e));
+        PackTotals tot{};
+        if (int rc = view_compact_offsets(c, 0, 0, &tot, &ms_index, who)) return rc;
+        HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+        e = launch_view_build_fill(src, v.vdi, v.stream);
+    } else {
+        e = launch_view_build(src, v.vdi, v.stream);
+    }
     if (e == hipSuccess) e = hipEventRecord(v.ev1, v.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
     if (e != hipSuccess) return fail(c, -3, std::string(who) + ": view_build_kernel: " + hipGetErrorString(e));
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_bind = ms;
+    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_bind = ms_index + ms;
     std::memcpy(v.pv_g, pv_g, sizeof v.pv_g);
     v.overlaps = 0;
     v.bound = true;
@@ -1965,20 +2017,32 @@ int view_merge(insitu_ctx* c, const ViewSource& src, int W, int H, int S, const 
     if (int rc = v.mg_totals.reserve(c, 1)) return rc;
     if (!v.h_mg_totals) HIPCHK(c, v.h_mg_totals.try_alloc(1));
     MergeTotals tot{};
-    float ms_count = 0.0f, ms_merge = 0.0f;
+    float ms_count = 0.0f, ms_merge = 0.0f, ms_index = 0.0f;
+    // compact: the count pass leaves every pixel's merged length as its count (the slots are known after it)
+    const bool compact = v.compact_next != 0;
+    if (compact)
+        if (int rc = view_reserve(c, W, H, 1)) return rc;
     HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-    if (int rc = view_merge_done(c, launch_view_merge_count(src, W, H, S, v.mg_totals, v.stream), who,
-                                 "view_merge_count_kernel", &tot, &ms_count))
+    if (int rc = view_merge_done(c, launch_view_merge_count(src, W, H, S, v.mg_totals, compact ? v.vdi.cnt : nullptr, v.stream),
+                                 who, "view_merge_count_kernel", &tot, &ms_count))
         return rc;
     if (tot.max_count > 255u)
         return fail(c, -1, std::string(who) + ": the merged lists hold up to " + std::to_string(tot.max_count) +
                                " entries per pixel, at most 255 can be bound");
-    if (int rc = view_reserve(c, W, H, tot.max_count > 0u ? (int)tot.max_count : 1)) return rc;
+    const int Sm = tot.max_count > 0u ? (int)tot.max_count : 1;
+    if (compact) {
+        v.vdi.S = Sm;
+        PackTotals ptot{};
+        HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+        if (int rc = view_compact_offsets(c, 0, 0, &ptot, &ms_index, who)) return rc;
+    } else if (int rc = view_reserve(c, W, H, Sm)) {
+        return rc;
+    }
     HIPCHK(c, hipEventRecord(v.ev0, v.stream));
     if (int rc = view_merge_done(c, launch_view_merge(src, S, v.vdi, v.mg_totals, v.stream), who, "view_merge_kernel", &tot,
                                  &ms_merge))
         return rc;
-    v.ms_bind = ms_count + ms_merge;
+    v.ms_bind = ms_count + ms_index + ms_merge;
     v.overlaps = (long long)tot.overlaps;
     std::memcpy(v.pv_g, pv_g, sizeof v.pv_g);
     v.bound = true;
@@ -2104,8 +2168,10 @@ namespace {
 
 // the offset buffers for the bound dimensions, the totals and their pinned copy; the offset passes
 // (pack_count_kernel, pack_scan_kernel) over the view's counts on the view's stream.  Blocks; *tot = what they
-// found, *ms = their HIP-event time.
-int pack_offsets(insitu_ctx* c, int check_E, unsigned long long expect_E, PackTotals* tot, float* ms, const char* who) {
+// found, *ms = their HIP-event time (timing_open: from the ev0 the caller has recorded, with its own pass over the
+// counts behind it).  A compact VDI in the making gets its loc with them.
+int pack_offsets(insitu_ctx* c, int check_E, unsigned long long expect_E, PackTotals* tot, float* ms, const char* who,
+                 bool timing_open) {
     ViewState& v = c->view;
     const uint64_t px = (uint64_t)v.vdi.W * (uint64_t)v.vdi.H;
     if (px > kPackMaxPixels) return fail(c, -1, std::string(who) + ": more than 2^30 pixels");
@@ -2114,8 +2180,9 @@ int pack_offsets(insitu_ctx* c, int check_E, unsigned long long expect_E, PackTo
     if ((rc = v.pk_totals.reserve(c, 1)) || (rc = v.pk_bstat.reserve(c, blocks)) || (rc = v.pk_boff.reserve(c, blocks)))
         return rc;
     if (!v.h_totals) HIPCHK(c, v.h_totals.try_alloc(1));
-    const PackOffsets o{v.vdi.cnt, v.pk_bstat, v.pk_boff, v.pk_totals, (uint32_t)px, (uint32_t)blocks};
-    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+    const PackOffsets o{v.vdi.cnt, v.pk_bstat, v.pk_boff, v.pk_totals, (uint32_t)px, (uint32_t)blocks,
+                        v.vdi.loc ? v.loc.get() : nullptr};
+    if (!timing_open) HIPCHK(c, hipEventRecord(v.ev0, v.stream));
     hipError_t e = launch_pack_offsets(o, v.vdi.S, check_E, expect_E, v.stream);
     if (e != hipSuccess) return fail(c, -3, std::string(who) + ": pack_count_kernel: " + hipGetErrorString(e));
     HIPCHK(c, hipEventRecord(v.ev1, v.stream));
@@ -2186,6 +2253,32 @@ int insitu_view_pack(insitu_ctx* c, int format, void* host_out, size_t cap, size
     if (bytes) *bytes = lay.total;
     if (!host_out || cap < lay.total)
         return fail(c, -1, "insitu_view_pack: output buffer too small (" + std::to_string(lay.total) + " bytes needed)");
+    if (v.vdi.loc) {
+        // compact: the bound VDI's arrays are the sections (FLOAT: three copies and no kernel, so ms_pack is 0;
+        // HALF: the colours converted element by element)
+        unsigned char* out = static_cast<unsigned char*>(host_out);
+        const bool half = format == INSITU_PACK_HALF;
+        if (half && h.E > 0)
+            if (int rc = v.pk_stage.reserve(c, lay.colour_bytes)) return rc;
+        HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+        if (half && h.E > 0) {
+            hipError_t e = launch_pack_convert(v.vdi.col, v.pk_stage, h.E, 1, v.stream);
+            if (e != hipSuccess) return fail(c, -3, std::string("pack_convert_kernel: ") + hipGetErrorString(e));
+        }
+        HIPCHK(c, hipEventRecord(v.ev1, v.stream));
+        HIPCHK(c, hipMemcpyAsync(out + kPackHeaderBytes, v.vdi.cnt, (size_t)lay.px, hipMemcpyDeviceToHost, v.stream));
+        if (h.E > 0) {
+            HIPCHK(c, hipMemcpyAsync(out + lay.depth_off, v.vdi.dep, lay.depth_bytes, hipMemcpyDeviceToHost, v.stream));
+            HIPCHK(c, hipMemcpyAsync(out + lay.colour_off, half ? (const void*)v.pk_stage.get() : (const void*)v.vdi.col,
+                                     lay.colour_bytes, hipMemcpyDeviceToHost, v.stream));
+        }
+        HIPCHK(c, hipStreamSynchronize(v.stream));
+        pack_write_header(out, h);
+        std::memset(out + kPackHeaderBytes + (size_t)lay.px, 0, lay.depth_off - kPackHeaderBytes - (size_t)lay.px);
+        float ms = 0.0f;
+        v.ms_pack = (half && h.E > 0 && hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) ? ms_count + ms : ms_count;
+        return 0;
+    }
     size_t colour_at = 0;
     if (int rc = pack_stage_reserve(c, lay, &colour_at)) return rc;
     PackParams p{};
@@ -2223,10 +2316,46 @@ int insitu_view_bind_packed(insitu_ctx* c, const void* data, size_t bytes) {
         return fail(c, -1, std::string("insitu_view_bind_packed: stream rejected: ") + why);
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (int rc = view_reserve(c, (int)h.W, (int)h.H, (int)h.S)) return rc;
+    const unsigned char* in = static_cast<const unsigned char*>(data);
+    if (v.vdi.loc) {
+        // compact: the counts, validated by the offset passes as below before anything depends on them; then the
+        // sections are the layout's arrays -- copied as they are, the HALF colours widened element by element
+        HIPCHK(c, hipMemcpyAsync(v.vdi.cnt, in + kPackHeaderBytes, (size_t)lay.px, hipMemcpyHostToDevice, v.stream));
+        PackTotals tot{};
+        float ms_count = 0.0f;
+        HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+        if (int rc = view_compact_offsets(c, 1, h.E, &tot, &ms_count, "insitu_view_bind_packed")) return rc;
+        if (tot.bad) {
+            if (tot.max_count > h.S)
+                return fail(c, -1, "insitu_view_bind_packed: stream rejected: a count of " + std::to_string(tot.max_count) +
+                                       " exceeds S = " + std::to_string(h.S));
+            return fail(c, -1, "insitu_view_bind_packed: stream rejected: the counts add up to " + std::to_string(tot.E) +
+                                   ", the header says " + std::to_string(h.E));
+        }
+        const bool half = h.format == kPackHalf;
+        if (half && h.E > 0)
+            if (int rc = v.pk_stage.reserve(c, lay.colour_bytes)) return rc;
+        if (h.E > 0) {
+            HIPCHK(c, hipMemcpyAsync(v.vdi.dep, in + lay.depth_off, lay.depth_bytes, hipMemcpyHostToDevice, v.stream));
+            HIPCHK(c, hipMemcpyAsync(half ? (void*)v.pk_stage.get() : (void*)v.vdi.col, in + lay.colour_off, lay.colour_bytes,
+                                     hipMemcpyHostToDevice, v.stream));
+        }
+        HIPCHK(c, hipEventRecord(v.ev0, v.stream));
+        hipError_t e = half ? launch_pack_convert(v.pk_stage, v.vdi.col, h.E, 0, v.stream) : hipSuccess;
+        if (e == hipSuccess) e = launch_view_tmax(v.vdi, v.stream);
+        if (e != hipSuccess) return fail(c, -3, std::string("pack_convert_kernel: ") + hipGetErrorString(e));
+        HIPCHK(c, hipEventRecord(v.ev1, v.stream));
+        HIPCHK(c, hipStreamSynchronize(v.stream));
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_pack = v.ms_bind = ms_count + ms;
+        std::memcpy(v.pv_g, h.pv_g, sizeof v.pv_g);
+        v.overlaps = 0;
+        v.bound = true;
+        return 0;
+    }
     size_t colour_at = 0;
     if (int rc = pack_stage_reserve(c, lay, &colour_at)) return rc;
     // the counts go straight into the view layout; nothing reads them as counts until they have been checked
-    const unsigned char* in = static_cast<const unsigned char*>(data);
     HIPCHK(c, hipMemcpyAsync(v.vdi.cnt, in + kPackHeaderBytes, (size_t)lay.px, hipMemcpyHostToDevice, v.stream));
     if (h.E > 0) {
         HIPCHK(c, hipMemcpyAsync(v.pk_stage, in + lay.depth_off, lay.depth_bytes, hipMemcpyHostToDevice, v.stream));
@@ -2361,6 +2490,17 @@ int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
     out->view_slots = c->view.bound ? c->view.vdi.S : 0;
     out->view_overlaps = c->view.bound ? c->view.overlaps : 0;
     out->ms_view_bind = c->view.ms_bind;
+    if (c->view.bound) {
+        ViewState& v = c->view;
+        float ms_count = 0.0f;   // (a dense bind counts its entries when they are first asked for)
+        if (int rc = pack_count_bound(c, &ms_count, "insitu_get_stats")) return rc;
+        ViewLayoutSize sz{};
+        const bool ok = v.vdi.loc ? view_compact_size(v.vdi.W, v.vdi.H, v.vdi.S, v.pk_E, &sz)
+                                  : view_dense_size(v.vdi.W, v.vdi.H, v.vdi.S, &sz);
+        out->view_entries = (long long)v.pk_E;
+        out->view_bytes = ok ? (long long)sz.bytes : 0;
+        out->view_compact = v.vdi.loc ? 1 : 0;
+    }
     out->ms_sample = out->ms_render;
     float a = 0.0f, b = 0.0f;
     if (c->mode == INSITU_MODE_VDI && f.ev_valid[EvRenderEnd] && span(EvRenderStart, EvSampleEnd, &a) &&

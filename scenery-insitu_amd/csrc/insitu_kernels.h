@@ -278,13 +278,29 @@ hipError_t launch_vdi_to_reference(const float4* color, const float2* depth, con
 // View layout of a bound VDI of dimensions (W, H, S): per pixel p = y*W + x (rows y-major) a count
 // cnt[p] and the list's entries at p*S + i, i < cnt[p] -- one contiguous run per list, horizontally
 // neighbouring lists neighbours in memory; per 8x8-pixel tile (index ty*tiles_x + tx) the largest count.
+//
+// The compact view layout (INSITU_OPT_VIEW_COMPACT; loc != null): cnt and tmax as above, col
+// and dep hold the E = sum of cnt[p] stored entries alone -- pixel by pixel in row-major p, each list first entry to
+// last, which is the order of the packed stream's depth and colour sections (vdi_pack_format.h): the two arrays
+// are the FLOAT stream's sections byte for byte.  Entry i of pixel p lies at boff[p >> 8] + loc[p] + i: boff the
+// 64-bit entry offset of each block of kPackBlockPx = 256 pixels (launch_pack_offsets), loc[p] the exclusive prefix
+// sum of the counts inside the pixel's block (16 bits: at most 255 pixels x 255 entries = 65 025 lie before a
+// block's last pixel).  3 bytes of index per pixel and 8 per block; S still bounds every count but sizes nothing.
+// The sizes of both layouts: vdi_view_layout.h.
 struct ViewVdi {
-    float4* col;     // W*H*S entries
+    float4* col;     // W*H*S entries (compact: max(E, 1))
     float2* dep;     // {start, end} depth in the generating view's NDC
     uint8_t* cnt;    // W*H
     uint8_t* tmax;   // tiles_x*tiles_y
     int W, H, S, tiles_x, tiles_y;
+    const unsigned long long* boff;   // compact: ceil(W*H / 256) block offsets; dense: null
+    const uint16_t* loc;              // compact: W*H offsets inside the block; dense: null
 };
+
+// where the list of pixel p begins in col/dep
+__host__ __device__ __forceinline__ size_t view_list_at(const ViewVdi& V, size_t p) {
+    return V.loc ? (size_t)V.boff[p >> 8] + (size_t)V.loc[p] : p * (size_t)V.S;
+}
 
 // What view_build_kernel and the merge kernels (vdi_view_merge.hip) read: n lists per pixel, list j of pixel (x, y)
 // with its entry k at col/dep[e0 + j*lstride + k*estride] (view_at, vdi_view_source.h).  Slotted (reference == 0):
@@ -316,8 +332,12 @@ struct ViewParams {
     uint32_t* out_image;  // (out_h, out_w) packed rgba8
 };
 
-hipError_t launch_view_build(const ViewSource& src, const ViewVdi& dst, hipStream_t s);
-hipError_t launch_vdi_view(const ViewParams& p, hipStream_t s);
+hipError_t launch_view_build(const ViewSource& src, const ViewVdi& dst, hipStream_t s);   // dense dst
+// the compact build's two passes: dst.cnt and dst.tmax alone; then, with dst.boff and dst.loc from
+// launch_pack_offsets over dst.cnt, the entries at their compact indices
+hipError_t launch_view_build_count(const ViewSource& src, const ViewVdi& dst, hipStream_t s);
+hipError_t launch_view_build_fill(const ViewSource& src, const ViewVdi& dst, hipStream_t s);
+hipError_t launch_vdi_view(const ViewParams& p, hipStream_t s);   // either layout (p.vdi.loc)
 
 // ---- the merged bind (vdi_view_merge.hip) ----
 struct MergeTotals {
@@ -325,10 +345,13 @@ struct MergeTotals {
     uint32_t pad;
     unsigned long long overlaps;   // adjacent merged entries whose next start lies before the previous end
 };
-// *tot zeroed on the stream, then max_count from the n lists of src over a W x H window of S-slot lists
-hipError_t launch_view_merge_count(const ViewSource& src, int W, int H, int S, MergeTotals* tot, hipStream_t s);
+// *tot zeroed on the stream, then max_count from the n lists of src over a W x H window of S-slot lists; cnt
+// non-null (the compact bind): every pixel's merged length, cut to 255, is also stored as cnt[y*W + x]
+hipError_t launch_view_merge_count(const ViewSource& src, int W, int H, int S, MergeTotals* tot, uint8_t* cnt,
+                                   hipStream_t s);
 // the k-way merge by start depth (lowest list on ties) of src's lists of S slots into dst (dst.S >= max_count):
-// dst's entries, counts and tile maxima, and tot->overlaps (zeroed on the stream first)
+// dst's entries, counts and tile maxima, and tot->overlaps (zeroed on the stream first).  A compact dst holds its
+// counts (launch_view_merge_count) and offsets already, and a list is written up to its count
 hipError_t launch_view_merge(const ViewSource& src, int S, const ViewVdi& dst, MergeTotals* tot, hipStream_t s);
 
 // ---- the packed VDI stream (vdi_pack.hip, vdi_pack_format.h) ----
@@ -342,12 +365,14 @@ struct PackTotals {
 
 // The offset passes over px = W*H counts: per block b of kPackBlockPx pixels bstat[b] = the sum of its counts |
 // the largest one << 24, boff[b] = the entries before its first pixel (64-bit), and the totals.
+// loc non-null (the compact view layout): per pixel the sum of the counts before it inside its block.
 struct PackOffsets {
     const uint8_t* cnt;
     uint32_t* bstat;
     unsigned long long* boff;
     PackTotals* totals;
     uint32_t px, nblocks;
+    uint16_t* loc;
 };
 
 // The cooperative copy between the view layout and the stream's sections: dep = E x {start, end}, col = E x rgba
@@ -365,5 +390,9 @@ hipError_t launch_pack_offsets(const PackOffsets& o, int S, int check_E, unsigne
 hipError_t launch_vdi_pack(const PackParams& p, hipStream_t s);     // view layout -> sections
 // sections -> view layout (vdi.cnt holds the stream's counts already, validated), then vdi.tmax from vdi.cnt
 hipError_t launch_vdi_unpack(const PackParams& p, hipStream_t s);
+// The compact view layout holds its entries in the sections' order, so the stream's colours convert element by
+// element: n rgba32f -> n 4 x binary16 (to_half) or back, entry e to entry e.
+hipError_t launch_pack_convert(const void* src, void* dst, unsigned long long n, int to_half, hipStream_t s);
+hipError_t launch_view_tmax(const ViewVdi& v, hipStream_t s);   // v.tmax from v.cnt
 
 }  // namespace insitu

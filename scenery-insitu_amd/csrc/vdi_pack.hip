@@ -12,6 +12,9 @@
 //     prefix values (256 B of LDS) -- so every section access of a wave is one contiguous piece (1 KiB of
 //     float colour) and the accesses to one list are contiguous too.
 // No atomics anywhere: the order of the bytes is a function of the counts alone.
+// The compact view layout (ViewVdi with loc) holds its entries in the sections' order already:
+// pack_count_kernel also leaves every pixel's offset inside its block (loc), the FLOAT stream is copied to and from
+// the layout's arrays as it is, and pack_convert_kernel converts the HALF colours element by element.
 #include "insitu_device.h"
 #include "insitu_kernels.h"
 #include "vdi_pack_format.h"
@@ -56,6 +59,11 @@ __global__ __launch_bounds__(256) void pack_count_kernel(const PackOffsets P) {
         s_max[wave] = mx;
     }
     __syncthreads();
+    if (P.loc && p < P.px) {   // the entries of the block before this pixel (at most 255 x 255: 16 bits hold it)
+        uint32_t before = sum - n;
+        for (int w = 0; w < wave; ++w) before += s_sum[w];
+        P.loc[p] = (uint16_t)before;
+    }
     if (threadIdx.x == 0) {
         const uint32_t a = s_max[0] > s_max[1] ? s_max[0] : s_max[1], b = s_max[2] > s_max[3] ? s_max[2] : s_max[3];
         P.bstat[blockIdx.x] = (s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3]) | ((a > b ? a : b) << 24);
@@ -166,6 +174,37 @@ __global__ __launch_bounds__(256) void view_tmax_kernel(const ViewVdi V) {
     if (lane == 0) V.tmax[tile] = (uint8_t)m;
 }
 
+// The compact view layout against the HALF stream: colour e of the one is colour e of the other.
+template <bool TO_HALF>
+__global__ __launch_bounds__(256) void pack_convert_kernel(const void* src, void* dst, unsigned long long n) {
+    const unsigned long long e = (unsigned long long)blockIdx.x * 256ull + (unsigned long long)threadIdx.x;
+    if (e >= n) return;
+    if constexpr (TO_HALF) {
+        const float4 c = static_cast<const float4*>(src)[e];
+        static_cast<uint2*>(dst)[e] = make_uint2(half2_of(c.x, c.y), half2_of(c.z, c.w));
+    } else {
+        const uint2 h = static_cast<const uint2*>(src)[e];
+        static_cast<float4*>(dst)[e] = make_float4(float_of_half(h.x & 0xffffu), float_of_half(h.x >> 16),
+                                                   float_of_half(h.y & 0xffffu), float_of_half(h.y >> 16));
+    }
+}
+
+hipError_t launch_pack_convert(const void* src, void* dst, unsigned long long n, int to_half, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const unsigned long long blocks = (n + 255ull) / 256ull;
+    if (!src || !dst || blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    if (to_half) hipLaunchKernelGGL(pack_convert_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, src, dst, n);
+    else hipLaunchKernelGGL(pack_convert_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, src, dst, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_view_tmax(const ViewVdi& v, hipStream_t s) {
+    const int tiles = v.tiles_x * v.tiles_y;
+    if (tiles <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(view_tmax_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, v);
+    return hipGetLastError();
+}
+
 hipError_t launch_pack_offsets(const PackOffsets& o, int S, int check_E, unsigned long long expect_E, hipStream_t s) {
     if (o.px == 0 || S < 1 || S > 255 || o.nblocks != (o.px + (uint32_t)kPackBlockPx - 1u) / (uint32_t)kPackBlockPx)
         return hipErrorInvalidValue;
@@ -179,7 +218,8 @@ hipError_t launch_pack_offsets(const PackOffsets& o, int S, int check_E, unsigne
 namespace {
 bool pack_params_ok(const PackParams& p) {
     const ViewVdi& v = p.vdi;
-    return v.W > 0 && v.H > 0 && v.S >= 1 && v.S <= 255 && (uint64_t)v.W * (uint64_t)v.H <= kPackMaxPixels;
+    // (the cooperative copies address the dense layout; a compact one is the sections already)
+    return !v.loc && v.W > 0 && v.H > 0 && v.S >= 1 && v.S <= 255 && (uint64_t)v.W * (uint64_t)v.H <= kPackMaxPixels;
 }
 unsigned pack_blocks(const PackParams& p) {
     const uint32_t px = (uint32_t)p.vdi.W * (uint32_t)p.vdi.H;
@@ -200,10 +240,7 @@ hipError_t launch_vdi_unpack(const PackParams& p, hipStream_t s) {
     else hipLaunchKernelGGL(vdi_unpack_kernel<false>, dim3(pack_blocks(p)), dim3(256), 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const int tiles = p.vdi.tiles_x * p.vdi.tiles_y;
-    if (tiles <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(view_tmax_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, p.vdi);
-    return hipGetLastError();
+    return launch_view_tmax(p.vdi, s);
 }
 
 }  // namespace insitu

@@ -9,6 +9,9 @@
 // (tile, cell), every crossing in closed form from the integer index of its plane, every supersegment
 // weighted by adjust_opacity(alpha, world length of the ray inside its box) and blended front to back as
 // vdi_flatten_kernel blends.  tests/view_ref/view_ref.c restates it operation for operation.
+// The compact view layout: view_build_count_kernel and view_build_fill_kernel build it in two
+// passes around the offset passes of vdi_pack.hip, and vdi_view_compact_kernel is vdi_view_kernel with a list's
+// first entry at boff[p >> 8] + loc[p] instead of p*S.
 #include "insitu_device.h"
 #include "insitu_kernels.h"
 #include "vdi_view_source.h"
@@ -47,11 +50,71 @@ __global__ __launch_bounds__(256) void view_build_kernel(const ViewSource P, con
     if (lane == 0) V.tmax[tile] = (uint8_t)m;
 }
 
-hipError_t launch_view_build(const ViewSource& src, const ViewVdi& dst, hipStream_t s) {
+// The compact layout's build, pass 1: the counts and the tiles' largest count as view_build_kernel
+// leaves them, nothing else.
+__global__ __launch_bounds__(256) void view_build_count_kernel(const ViewSource P, const ViewVdi V) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tile = (int)blockIdx.x * 4 + wave;
+    if (tile >= V.tiles_x * V.tiles_y) return;   // wave-uniform
+    const int ty = tile / V.tiles_x, tx = tile - ty * V.tiles_x;
+    const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
+    const int S = V.S, H = V.H;
+    int n = 0;
+    if (x < V.W && y < H) {
+        const ViewAt at = view_at(P, x, y, H, S);
+        const int stored = view_slots(P, 0, x, y, S);
+        while (n < stored && P.dep[at.e0 + (size_t)n * at.estride].x != 0.0f) ++n;
+        V.cnt[(size_t)y * (size_t)V.W + (size_t)x] = (uint8_t)n;
+    }
+    int m = n;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int v = __shfl_xor(m, o);
+        m = v > m ? v : m;
+    }
+    if (lane == 0) V.tmax[tile] = (uint8_t)m;
+}
+
+// ... pass 2, once the offsets of those counts are known: the first cnt[p] entries of every list, at
+// boff[p >> 8] + loc[p]
+__global__ __launch_bounds__(256) void view_build_fill_kernel(const ViewSource P, const ViewVdi V) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tile = (int)blockIdx.x * 4 + wave;
+    if (tile >= V.tiles_x * V.tiles_y) return;   // wave-uniform
+    const int ty = tile / V.tiles_x, tx = tile - ty * V.tiles_x;
+    const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
+    if (x >= V.W || y >= V.H) return;
+    const size_t p = (size_t)y * (size_t)V.W + (size_t)x;
+    const size_t o = (size_t)V.boff[p >> 8] + (size_t)V.loc[p];
+    const ViewAt at = view_at(P, x, y, V.H, V.S);
+    const int n = (int)V.cnt[p];
+    for (int i = 0; i < n; ++i) {
+        const size_t e = at.e0 + (size_t)i * at.estride;
+        V.col[o + i] = P.col[e];
+        V.dep[o + i] = P.dep[e];
+    }
+}
+
+namespace {
+template <class Kernel>
+hipError_t launch_build(Kernel kernel, const ViewSource& src, const ViewVdi& dst, hipStream_t s) {
     const int tiles = dst.tiles_x * dst.tiles_y;
     if (tiles <= 0 || dst.S <= 0 || dst.S > 255) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(view_build_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, src, dst);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, src, dst);
     return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_view_build(const ViewSource& src, const ViewVdi& dst, hipStream_t s) {
+    if (dst.loc) return hipErrorInvalidValue;
+    return launch_build(view_build_kernel, src, dst, s);
+}
+hipError_t launch_view_build_count(const ViewSource& src, const ViewVdi& dst, hipStream_t s) {
+    return launch_build(view_build_count_kernel, src, dst, s);
+}
+hipError_t launch_view_build_fill(const ViewSource& src, const ViewVdi& dst, hipStream_t s) {
+    if (!dst.loc || !dst.boff) return hipErrorInvalidValue;
+    return launch_build(view_build_fill_kernel, src, dst, s);
 }
 
 namespace {
@@ -153,9 +216,10 @@ __device__ __forceinline__ void dda(const RayG& r, float ra, float rb, int g, in
     }
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(256) void vdi_view_kernel(const ViewParams P) {
+// One output pixel's ray through the bound VDI.  COMPACT selects where a list begins (ViewVdi) and nothing else: every
+// float operation and its order is the same in both layouts.
+template <bool COMPACT>
+__device__ __forceinline__ void view_ray(const ViewParams& P) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int otx = (P.out_w + 7) >> 3;
     const int tile = (int)blockIdx.x * 4 + wave;
@@ -201,8 +265,9 @@ __global__ __launch_bounds__(256) void vdi_view_kernel(const ViewParams P) {
         auto cell = [&](int kx, int ky, float sa, float sb) {
             const size_t p = (size_t)ky * (size_t)W + (size_t)kx;
             const int n = (int)V.cnt[p];
-            const float4* col = V.col + p * (size_t)S;
-            const float2* dep = V.dep + p * (size_t)S;
+            const size_t at = COMPACT ? (size_t)V.boff[p >> 8] + (size_t)V.loc[p] : p * (size_t)S;
+            const float4* col = V.col + at;
+            const float2* dep = V.dep + at;
             for (int j = 0; j < n; ++j) {
                 const int i = back ? n - 1 - j : j;
                 const float2 se = dep[i];
@@ -245,11 +310,18 @@ __global__ __launch_bounds__(256) void vdi_view_kernel(const ViewParams P) {
     P.out_image[o] = unorm8(C0) | (unorm8(C1) << 8) | (unorm8(C2) << 16) | (unorm8(C3) << 24);
 }
 
+}  // namespace
+
+__global__ __launch_bounds__(256) void vdi_view_kernel(const ViewParams P) { view_ray<false>(P); }
+__global__ __launch_bounds__(256) void vdi_view_compact_kernel(const ViewParams P) { view_ray<true>(P); }
+
 hipError_t launch_vdi_view(const ViewParams& p, hipStream_t s) {
     if (p.out_w <= 0 || p.out_h <= 0) return hipErrorInvalidValue;
     const long long tiles = (long long)((p.out_w + 7) / 8) * (long long)((p.out_h + 7) / 8);
     if (tiles > 0x7fffffffLL / 4) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(vdi_view_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, p);
+    if (p.vdi.loc && !p.vdi.boff) return hipErrorInvalidValue;
+    if (p.vdi.loc) hipLaunchKernelGGL(vdi_view_compact_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(vdi_view_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

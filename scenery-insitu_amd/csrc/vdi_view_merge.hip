@@ -9,6 +9,9 @@
 // view_merge_kernel: the merge into the view layout (ViewVdi) -- entries, counts, the tiles' largest count -- and
 // the number of adjacent merged entries that overlap in depth.
 // Both: one lane per VDI pixel, one wave per 8x8 tile, as view_build_kernel.
+// For the compact view layout the count kernel also stores every pixel's merged length as its
+// count, the offset passes of vdi_pack.hip run between the two kernels, and the merge writes each list where
+// view_list_at puts it.
 #include "insitu_device.h"
 #include "insitu_kernels.h"
 #include "vdi_view_source.h"
@@ -31,7 +34,7 @@ __device__ __forceinline__ int wave_max(int m) {
 }  // namespace
 
 __global__ __launch_bounds__(256) void view_merge_count_kernel(const ViewSource P, const int W, const int H, const int S,
-                                                               MergeTotals* tot) {
+                                                               MergeTotals* tot, uint8_t* cnt) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int tiles_x = (W + 7) >> 3, tiles_y = (H + 7) >> 3;
     const int tile = (int)blockIdx.x * 4 + wave;
@@ -41,13 +44,21 @@ __global__ __launch_bounds__(256) void view_merge_count_kernel(const ViewSource 
     int m = 0;
     if (x < W && y < H) {
         const ViewAt at = view_at(P, x, y, H, S);
+        int taken = 0;   // the entries the merge takes: a list also ends at a start the merge never picks (not < 100000)
         for (int j = 0; j < P.n; ++j) {
             const int slots = view_slots(P, j, x, y, S);
             const size_t e0 = at.e0 + (size_t)j * at.lstride;
-            int c = 0;
-            while (c < slots && P.dep[e0 + (size_t)c * at.estride].x != 0.0f) ++c;
+            int c = 0, t = -1;
+            for (; c < slots; ++c) {
+                const float start = P.dep[e0 + (size_t)c * at.estride].x;
+                if (start == 0.0f) break;
+                if (t < 0 && !(start < 100000.0f)) t = c;
+            }
             m += c;
+            taken += t < 0 ? c : t;
         }
+        // the compact bind: the merged list's length is the pixel's count (more than 255 anywhere rejects the bind)
+        if (cnt) cnt[(size_t)y * (size_t)W + (size_t)x] = (uint8_t)(taken < 255 ? taken : 255);
     }
     m = wave_max(m);
     if (lane == 0 && m > 0) atomicMax(&tot->max_count, (uint32_t)m);
@@ -91,9 +102,11 @@ __global__ __launch_bounds__(256) void view_merge_kernel(const ViewSource P, con
             }
         }
         const size_t p = (size_t)y * (size_t)V.W + (size_t)x;
-        const size_t o = p * (size_t)Sm;
+        const size_t o = view_list_at(V, p);
+        // (the count kernel sized Sm, and a compact list's own room: the bound never cuts a list short)
+        const int room = V.loc ? ((int)V.cnt[p] < Sm ? (int)V.cnt[p] : Sm) : Sm;
         float prev_end = 0.0f;
-        while (m < Sm) {   // (the count kernel sized Sm: the bound never cuts a list short)
+        while (m < room) {
             // determineNextSupseg (VDICompositor.comp:58-91): smallest non-zero front start, lowest index on ties
             float low = 100000.0f;
             int idx = -1;
@@ -137,7 +150,7 @@ __global__ __launch_bounds__(256) void view_merge_kernel(const ViewSource P, con
             V.dep[o + (size_t)m] = se;
             ++m;
         }
-        V.cnt[p] = (uint8_t)m;
+        if (!V.loc) V.cnt[p] = (uint8_t)m;   // (compact: the offsets stand on the count kernel's counts)
     }
     const int mx = wave_max(m);
 #pragma unroll
@@ -160,18 +173,20 @@ unsigned merge_blocks(int W, int H) {
 
 }  // namespace
 
-hipError_t launch_view_merge_count(const ViewSource& src, int W, int H, int S, MergeTotals* tot, hipStream_t s) {
+hipError_t launch_view_merge_count(const ViewSource& src, int W, int H, int S, MergeTotals* tot, uint8_t* cnt,
+                                   hipStream_t s) {
     const unsigned blocks = merge_blocks(W, H);
     if (!blocks || S <= 0 || src.n < 1 || src.n > kMaxLists) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(tot, 0, sizeof(MergeTotals), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(view_merge_count_kernel, dim3(blocks), dim3(256), 0, s, src, W, H, S, tot);
+    hipLaunchKernelGGL(view_merge_count_kernel, dim3(blocks), dim3(256), 0, s, src, W, H, S, tot, cnt);
     return hipGetLastError();
 }
 
 hipError_t launch_view_merge(const ViewSource& src, int S, const ViewVdi& dst, MergeTotals* tot, hipStream_t s) {
     const unsigned blocks = merge_blocks(dst.W, dst.H);
-    if (!blocks || S <= 0 || dst.S <= 0 || dst.S > 255 || src.n < 1 || src.n > kMaxLists) return hipErrorInvalidValue;
+    if (!blocks || S <= 0 || dst.S <= 0 || dst.S > 255 || src.n < 1 || src.n > kMaxLists || (dst.loc && !dst.boff))
+        return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(&tot->overlaps, 0, sizeof tot->overlaps, s);
     if (e != hipSuccess) return e;
     if (src.n <= 8) hipLaunchKernelGGL(view_merge_kernel<8>, dim3(blocks), dim3(256), 0, s, src, S, dst, tot);

@@ -22,7 +22,7 @@ except Exception:  # pragma: no cover - torch is always present in this image
 PKG_ROOT = Path(__file__).resolve().parent.parent
 LIB_PATH = Path(os.environ.get("INSITU_HIP_LIB", PKG_ROOT / "lib" / "libinsitu_hip.so"))
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 COMM_ID_BYTES = 128
 
 MODE_PLAIN, MODE_VDI = 0, 1
@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = (
 OPT_EXACT_SEARCH, OPT_SEARCH_DEPTH, OPT_LONG_SAMPLES, OPT_ROUND_BATCH, OPT_SEARCH_OVERSUB, OPT_TILE_ORDER = range(6)
 OPT_SUPER_TILE, OPT_REGROUP, OPT_EXACT_TILE_KEYS, OPT_PIPE_TRIGGER, OPT_PIPE_OVERSUB, OPT_PIPE_SEARCH_RAYS = 8, 9, 10, 11, 12, 13
 OPT_VIEW_SKIP = 14
+OPT_VIEW_COMPACT = 15
 
 F16 = ctypes.c_float * 16
 
@@ -88,6 +89,7 @@ class Stats(ctypes.Structure):
         ("ms_image_d2h", ctypes.c_float), ("ms_latency", ctypes.c_float), ("pipelined", ctypes.c_int),
         ("ms_ingest", ctypes.c_float), ("ms_view", ctypes.c_float), ("ms_pack", ctypes.c_float),
         ("view_slots", ctypes.c_int), ("view_overlaps", ctypes.c_longlong), ("ms_view_bind", ctypes.c_float),
+        ("view_entries", ctypes.c_longlong), ("view_bytes", ctypes.c_longlong), ("view_compact", ctypes.c_int),
     ]
 
 

@@ -321,6 +321,9 @@ class InSituContext:
         self._check(self.lib.insitu_view_bind_packed(self.h, b.ctypes.data, b.nbytes), "insitu_view_bind_packed")
 
     def stats(self) -> dict:
+        """insitu_stats as a dictionary, one key per field of native.Stats: the last frame's times and counters, and
+        of the bound VDI view_slots, view_overlaps, view_entries (its stored entries), view_bytes (device bytes of
+        its view layout) and view_compact (1: bound with native.OPT_VIEW_COMPACT set)."""
         st = native.Stats()
         self._check(self.lib.insitu_get_stats(self.h, ctypes.byref(st)), "insitu_get_stats")
         return {k: getattr(st, k) for k, _ in native.Stats._fields_}

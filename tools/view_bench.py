@@ -23,8 +23,13 @@ the same orbit (skip on).  Then, in the same process, the same bricks in a compo
 gathered VDI; per camera the largest and the mean absolute difference of the two rgba8 images, in LSB -- what the
 VDICompositor's re-supersegmentation to S_out entries costs a novel view.  Prints one JSON line and nothing else runs.
 
-usage: python tools/view_bench.py [--brick 512] [--sim-n 512] [--views 36] [--passes 3] [--count-views 2] [--pack]
-       python tools/view_bench.py --merged [--brick 512] [--sim-n 512] [--views 36] [--passes 2]
+--compact: every measurement is also taken with INSITU_OPT_VIEW_COMPACT = 1, the same VDI
+bound again in the compact view layout: the layout's device bytes (insitu_stats.view_bytes) and the bind's kernels,
+the orbit with its passes alternating between the two layouts, with --pack the pack and bind-packed times, with
+--merged the merged bind and its orbit.  The compact figures stand beside the dense ones in the JSON.
+
+usage: python tools/view_bench.py [--brick 512] [--sim-n 512] [--views 36] [--passes 3] [--count-views 2] [--pack] [--compact]
+       python tools/view_bench.py --merged [--compact] [--brick 512] [--sim-n 512] [--views 36] [--passes 2]
 """
 from __future__ import annotations
 
@@ -78,42 +83,63 @@ def run_merged(args):
             for i in range(args.views)]
     ow, oh = args.out_w, args.out_h
 
-    def orbit(ctx):
-        """(best ms per camera over the timed passes after one warm-up pass, the images)"""
-        ms, imgs = [], None
+    def orbit(ctx, layouts=(None,), source=None):
+        """Per layout (None: as bound; 0 / 1: `source` bound again dense / compact before each of its passes, so
+        the layouts alternate): (best ms per camera over the timed passes after one warm-up pass, the images)"""
+        ms, imgs = {lay: [] for lay in layouts}, {}
         for k in range(args.passes + 1):
-            row, imgs = [], []
-            for cam in cams:
-                imgs.append(ctx.view_render(cam, ow, oh))
-                row.append(ctx.stats()["ms_view"])
-            if k:
-                ms.append(row)
-        return np.asarray(ms).min(axis=0), imgs
+            for lay in layouts:
+                if lay is not None:
+                    ctx.set_option(native.OPT_VIEW_COMPACT, lay)
+                    ctx.view_bind(source)
+                row, imgs[lay] = [], []
+                for cam in cams:
+                    imgs[lay].append(ctx.view_render(cam, ow, oh))
+                    row.append(ctx.stats()["ms_view"])
+                if k:
+                    ms[lay].append(row)
+        return {lay: (np.asarray(ms[lay]).min(axis=0), imgs[lay]) for lay in layouts}
+
+    def bind_merged(layout):
+        flat.set_option(native.OPT_VIEW_COMPACT, layout)
+        ms_bind, wall_bind = [], []
+        for _ in range(4):   # one warm-up (it allocates), then the best of three
+            t0 = time.perf_counter()
+            flat.view_bind(native.VIEW_MERGED)
+            wall_bind.append((time.perf_counter() - t0) * 1e3)
+            ms_bind.append(flat.stats()["ms_view_bind"])
+        st = flat.stats()
+        return {"view_slots": int(st["view_slots"]), "entries": int(st["view_entries"]), "view_overlaps": int(st["view_overlaps"]),
+                "ms_view_bind": min(ms_bind[1:]), "ms_view_bind_first": ms_bind[0], "ms_bind_wall": min(wall_bind[1:]),
+                "view_layout_bytes": int(st["view_bytes"]), "view_compact": int(st["view_compact"])}
 
     flat.frame(cams[0])
-    ms_bind, wall_bind = [], []
-    for _ in range(4):   # one warm-up (it allocates), then the best of three
-        t0 = time.perf_counter()
-        flat.view_bind(native.VIEW_MERGED)
-        wall_bind.append((time.perf_counter() - t0) * 1e3)
-        ms_bind.append(flat.stats()["ms_view_bind"])
-    st = flat.stats()
+    merged = bind_merged(0)
     px16 = (W_IMG * H_IMG + 15) // 16 * 16
     sizes = {name: int(flat.lib.insitu_view_pack_bytes(flat.h, fmt))
              for name, fmt in (("float", native.PACK_FLOAT), ("half", native.PACK_HALF))}
-    entries = (sizes["float"] - PACK_HEADER_BYTES - px16) // ENTRY_BYTES
-    merged = {"view_slots": int(st["view_slots"]), "entries": int(entries), "view_overlaps": int(st["view_overlaps"]),
-              "ms_view_bind": min(ms_bind[1:]), "ms_view_bind_first": ms_bind[0], "ms_bind_wall": min(wall_bind[1:]),
-              "packed_bytes": sizes, "view_layout_bytes": int(st["view_slots"]) * W_IMG * H_IMG * ENTRY_BYTES,
-              "slots_if_sized_by_n_times_S": len(bricks) * S}
+    assert merged["entries"] == (sizes["float"] - PACK_HEADER_BYTES - px16) // ENTRY_BYTES
+    merged.update({"packed_bytes": sizes, "slots_if_sized_by_n_times_S": len(bricks) * S})
     log(f"view_bench: merged bind {json.dumps(merged)}")
-    ms_m, img_m = orbit(flat)
+    compact = None
+    if args.compact:
+        compact = bind_merged(1)
+        log(f"view_bench: compact merged bind {json.dumps(compact)}")
+        runs = orbit(flat, (0, 1), native.VIEW_MERGED)
+        ms_m, img_m = runs[0]
+        ms_c, img_c = runs[1]
+        assert all(np.array_equal(a, b) for a, b in zip(img_m, img_c)), "compact and dense images differ"
+        compact.update({"ms_per_view": float(ms_c.mean()), "ms_min_max": [float(ms_c.min()), float(ms_c.max())],
+                        "ms_by_view": [round(float(v), 4) for v in ms_c]})
+        flat.set_option(native.OPT_VIEW_COMPACT, 0)
+    else:
+        ms_m, img_m = orbit(flat)[None]
     flat.close()
 
     comp.frame(cams[0])
     comp.view_bind(native.VIEW_GATHERED)
     g_entries = (int(comp.lib.insitu_view_pack_bytes(comp.h, native.PACK_FLOAT)) - PACK_HEADER_BYTES - px16) // ENTRY_BYTES
-    ms_g, img_g = orbit(comp)
+    ms_g, img_g = orbit(comp)[None]
     comp.close()
     lsb_max, lsb_mean = [], []
     for a, b in zip(img_m, img_g):
@@ -125,6 +151,7 @@ def run_merged(args):
                   f"({W_IMG}x{H_IMG}, S = S_out = {S}, 8x{n}^3 volume)",
         "views": args.views, "passes": args.passes,
         "merged": merged, "gathered": {"view_slots": S, "entries": int(g_entries)},
+        "merged_compact": compact,   # --compact: the same bind and orbit in the compact layout, alternating with dense
         "ms_per_view": {"merged": float(ms_m.mean()), "gathered": float(ms_g.mean())},
         "ms_min_max": {"merged": [float(ms_m.min()), float(ms_m.max())], "gathered": [float(ms_g.min()), float(ms_g.max())]},
         "ms_by_view_merged": [round(float(v), 4) for v in ms_m],
@@ -149,6 +176,8 @@ def main():
     ap.add_argument("--out-w", type=int, default=W_IMG)
     ap.add_argument("--out-h", type=int, default=H_IMG)
     ap.add_argument("--pack", action="store_true", help="also time the packed stream of the bound VDI, both formats")
+    ap.add_argument("--compact", action="store_true",
+                    help="every measurement also in the compact view layout (INSITU_OPT_VIEW_COMPACT), beside dense")
     ap.add_argument("--merged", action="store_true",
                     help="INSITU_VIEW_MERGED of the flatten context against INSITU_VIEW_GATHERED of the composite_vdi one")
     args = ap.parse_args()
@@ -180,15 +209,31 @@ def main():
 
     gen_cam = cam_at(0)
     ctx.frame(gen_cam)
-    ctx.view_bind(native.VIEW_GATHERED)
+    layouts = (0, 1) if args.compact else (0,)   # INSITU_OPT_VIEW_COMPACT: dense, and beside it compact
+    names = {0: "dense", 1: "compact"}
     cams = [cam_at(i) for i in range(args.views)]
     ow, oh = args.out_w, args.out_h
 
-    pack = None
-    if args.pack:
-        pack = {"dense_readback_bytes": W_IMG * H_IMG * S * 24,
-                "timing": "one warm-up, then the best of three; ms_pack: HIP events around the kernels alone"}
+    def bind(layout):
+        ctx.set_option(native.OPT_VIEW_COMPACT, layout)
+        ctx.view_bind(native.VIEW_GATHERED)
+
+    layout_info = {}
+    for layout in layouts:
+        ms_bind = []
+        for _ in range(4):   # one warm-up (it allocates), then the best of three
+            bind(layout)
+            ms_bind.append(ctx.stats()["ms_view_bind"])
+        st = ctx.stats()
+        layout_info[names[layout]] = {"view_bytes": int(st["view_bytes"]), "view_entries": int(st["view_entries"]),
+                                      "view_compact": int(st["view_compact"]), "ms_view_bind": min(ms_bind[1:]),
+                                      "ms_view_bind_first": ms_bind[0]}
+    log(f"view_bench: layouts {json.dumps(layout_info)}")
+
+    def time_pack(layout):
+        res = {}
         for name, fmt in (("float", native.PACK_FLOAT), ("half", native.PACK_HALF)):
+            bind(layout)
             ms_pack, ms_wall, ms_unpack, ms_bind_wall = [], [], [], []
             for _ in range(4):
                 t0 = time.perf_counter()
@@ -202,13 +247,22 @@ def main():
                 ms_unpack.append(ctx.stats()["ms_pack"])
             if fmt == native.PACK_FLOAT:   # (the round trip is exact: the same bytes again)
                 assert np.array_equal(ctx.view_pack(fmt), stream)
-            pack[name] = {"bytes": int(stream.size), "ms_pack_kernels_with_count": ms_pack[0], "ms_pack_kernels": min(ms_pack[1:]), "ms_pack_wall": min(ms_wall[1:]),
-                          "ms_unpack_kernels": min(ms_unpack[1:]), "ms_bind_packed_wall": min(ms_bind_wall[1:])}
+            res[name] = {"bytes": int(stream.size), "ms_pack_kernels_with_count": ms_pack[0], "ms_pack_kernels": min(ms_pack[1:]), "ms_pack_wall": min(ms_wall[1:]),
+                         "ms_unpack_kernels": min(ms_unpack[1:]), "ms_bind_packed_wall": min(ms_bind_wall[1:])}
             del stream
-            ctx.view_bind(native.VIEW_GATHERED)   # (the orbit below views the exact VDI)
+        return res
+
+    pack = None
+    if args.pack:
+        pack = {"dense_readback_bytes": W_IMG * H_IMG * S * 24,
+                "timing": "one warm-up, then the best of three; ms_pack: HIP events around the kernels alone"}
+        pack.update(time_pack(0))
+        if args.compact:
+            pack["compact"] = time_pack(1)
         log(f"view_bench: pack {json.dumps(pack)}")
 
-    def orbit(skip):
+    def orbit(layout, skip):
+        bind(layout)   # (the orbit views the exact VDI; with --compact the layouts alternate)
         ctx.set_option(native.OPT_VIEW_SKIP, skip)
         ms = []
         for cam in cams:
@@ -216,15 +270,26 @@ def main():
             ms.append(ctx.stats()["ms_view"])
         return ms
 
-    for skip in (1, 0):   # warm-up: every camera, both settings
-        orbit(skip)
-    times = {1: [], 0: []}
+    settings = [(layout, skip) for layout in layouts for skip in (1, 0)]
+    for layout, skip in settings:   # warm-up: every camera, every setting
+        orbit(layout, skip)
+    all_times = {k: [] for k in settings}
     for _ in range(args.passes):
-        for skip in (1, 0):
-            times[skip].append(orbit(skip))
+        for k in settings:
+            all_times[k].append(orbit(*k))
     ctx.set_option(native.OPT_VIEW_SKIP, 1)
-    per_view = {k: np.asarray(v).min(axis=0) for k, v in times.items()}    # best of the passes, per camera
+    bind(0)
+    best = {k: np.asarray(v).min(axis=0) for k, v in all_times.items()}    # best of the passes, per camera
+    times = {skip: all_times[(0, skip)] for skip in (1, 0)}
+    per_view = {skip: best[(0, skip)] for skip in (1, 0)}
     spread = {k: float(np.max(np.asarray(v).max(axis=0) / np.asarray(v).min(axis=0))) for k, v in times.items()}
+    compact = None
+    if args.compact:
+        compact = {"ms_per_view": {"skip": float(best[(1, 1)].mean()), "walk": float(best[(1, 0)].mean())},
+                   "ms_min_max": {"skip": [float(best[(1, 1)].min()), float(best[(1, 1)].max())],
+                                  "walk": [float(best[(1, 0)].min()), float(best[(1, 0)].max())]},
+                   "ms_by_view_skip": [round(float(v), 4) for v in best[(1, 1)]],
+                   "ms_by_view_walk": [round(float(v), 4) for v in best[(1, 0)]]}
 
     dep = ctx.read(native.BUF_GATHERED_DEPTH)
     counts = np.count_nonzero(dep[:, :, 0::2], axis=2)
@@ -262,6 +327,8 @@ def main():
                 "empty_tile_fraction": tiles_empty},
         "work": work,
         "pack": pack,
+        "layouts": layout_info,   # view_bytes and the bind's kernels per view layout
+        "compact": compact,       # --compact: the orbit in the compact layout, its passes alternating with dense
         "timing": "HIP events around vdi_view_kernel (insitu_stats.ms_view), best of the passes per camera",
     }
     ctx.close()
