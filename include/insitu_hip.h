@@ -288,9 +288,10 @@ int insitu_read_region(insitu_ctx* ctx, int which, int slot, int x0, int x1, voi
  * frame and 0 <= slot < the context's sub-VDIs.  INSITU_VIEW_MERGED (slot 0) binds all of the rank's sub-VDIs of
  * that frame as one VDI: per pixel their lists merged by start depth, the lowest slot first on a tie, as the
  * flatten compositor walks them (VDICompositor.comp:58-91), every entry copied bit for bit.  The bound VDI has
- * S_m = max(1, the longest merged list) slots (insitu_stats.view_slots); more than 255 is rejected with -1 and
- * leaves no VDI bound, as every failed merged bind does.  With one sub-VDI (one brick, merge_bricks) it is
- * INSITU_VIEW_BRICK of slot 0; with nranks > 1 it merges the rank's own bricks only. */
+ * S_m = max(1, the longest merged list) slots (insitu_stats.view_slots); more than 255 is rejected with -1.
+ * With one sub-VDI (one brick, merge_bricks) it is INSITU_VIEW_BRICK of slot 0; with nranks > 1 it merges the
+ * rank's own bricks only.
+ * A failed insitu_view_bind* call leaves no VDI bound -- whichever of the four it is, and wherever it fails. */
 int insitu_view_bind(insitu_ctx* ctx, int source, int slot);
 /* The same from host memory: a VDI in the reference layout -- colour (W,H,S,4) rgba32f and depth (W,H,2S) r32f, x
  * slowest, as the dumps hold it (vdi_io.read_vdi) -- with the camera that generated it.  W, H and S (1..255) need
@@ -300,7 +301,7 @@ int insitu_view_bind_host(insitu_ctx* ctx, const void* color, const void* depth,
                           const insitu_camera* gen_cam);
 /* The merged bind from host memory: n (1..32) such VDIs of one W, H, S and one generating camera -- the per-rank
  * dumps of a frame, say (DistributedVolumes.kt:848-849) -- merged as INSITU_VIEW_MERGED merges, colors[j] / depths[j]
- * taking the place of slot j.  n = 1 is insitu_view_bind_host.  A failed call leaves no VDI bound. */
+ * taking the place of slot j.  n = 1 is insitu_view_bind_host. */
 int insitu_view_bind_host_set(insitu_ctx* ctx, const void* const* colors, const void* const* depths, int n, int W,
                               int H, int S, const insitu_camera* gen_cam);
 /* Render the bound VDI from `cam` at out_w x out_h and block until it is done.  host_out non-NULL: receives the
@@ -326,7 +327,7 @@ size_t insitu_view_pack_bytes(insitu_ctx* ctx, int format);
 int insitu_view_pack(insitu_ctx* ctx, int format, void* host_out, size_t cap, size_t* bytes);
 /* Bind the VDI of a packed stream (either format; W, H and S need not be the context's), as insitu_view_bind_host
  * does for the dense layout.  The header and `bytes` are checked on the host, the counts on the device before
- * anything is placed by them; a rejected stream returns -1 and leaves no VDI bound.  The receiving end of
+ * anything is placed by them; a rejected stream returns -1.  The receiving end of
  * VolumeFromFileExample.kt:907-1030 (the remote viewer's upload of the message). */
 int insitu_view_bind_packed(insitu_ctx* ctx, const void* data, size_t bytes);
 int insitu_get_stats(insitu_ctx* ctx, insitu_stats* out);

@@ -1,20 +1,17 @@
 // insitu_hip.cpp -- host side of libinsitu_hip.so: the C ABI declared in include/insitu_hip.h.
 //
 // Owns the per-rank device state of the in-situ frame (bricks, transfer function, sub-VDI
-// send/receive blocks, octree counters, composited strip, gathered image) and orders the
-// four stages on one HIP stream:
+// send/receive blocks, octree counters, composited strip, gathered image; the types: insitu_host.h) and orders
+// the four stages of a frame (unpipelined: on one HIP stream; insitu_frame_pipelined: over the sampling, search and
+// completion streams):
 //   render    -> VDIGenerator.comp+AccumulateVDI.comp / VolumeRaycaster.comp+AccumulatePlainImage.comp
 //   exchange  -> distributeVDIs' MPI_Alltoall (DistributedVolumes.kt:860), here RCCL send/recv
 //                of contiguous screen-strip blocks over xGMI
 //   composite -> PlainImageCompositor.comp / VDI flatten (VDIGenerator.comp:147-185)
 //   gather    -> gatherCompositedVDIs' MPI_Gather (DistributedVolumes.kt:903), RCCL to rank 0
-#include "insitu_hip.h"
-#include "insitu_kernels.h"
-#include "vdi_pack_format.h"
-#include "vdi_view_layout.h"
-
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
+// The novel-view subsystem (insitu_view_*) is insitu_view.cpp: its own stream, buffers and blocking calls.  This
+// file only frees its state (release), sets its options, reads its output buffers and asks it for its statistics.
+#include "insitu_host.h"
 
 #include <cmath>
 #include <cstdio>
@@ -27,347 +24,13 @@
 
 #pragma clang fp contract(off)
 
-using namespace insitu;
-
 namespace {
 
 thread_local std::string g_create_error;
 
-int fail(insitu_ctx* c, int code, const std::string& msg);
-
-// Owner of one device allocation of `count()` elements (Pinned: of page-locked host memory), freed when it goes
-// out of scope: with the context, a frame slot, the view state or a brick, or at the end of a readback.  Reads as
-// the T* it holds.
-template <typename T, bool Pinned = false>
-class DevBuf {
-public:
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        if (this != &o) {
-            reset();
-            std::swap(p_, o.p_);
-            std::swap(n_, o.n_);
-        }
-        return *this;
-    }
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { reset(); }
-
-    operator T*() const { return p_; }
-    T* operator->() const { return p_; }
-    T* get() const { return p_; }
-    size_t count() const { return n_; }
-
-    void reset() {
-        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
-        p_ = nullptr;
-        n_ = 0;
-    }
-    // frees what it holds, then allocates `count` elements (0: none); on failure it is left empty and the error is
-    // returned, not reported
-    hipError_t try_alloc(size_t count) {
-        reset();
-        if (count == 0) return hipSuccess;
-        const hipError_t e = Pinned ? hipHostMalloc((void**)&p_, count * sizeof(T), 0) : hipMalloc((void**)&p_, count * sizeof(T));
-        if (e != hipSuccess) {
-            p_ = nullptr;
-            (void)hipGetLastError();
-            return e;
-        }
-        n_ = count;
-        return hipSuccess;
-    }
-    // the same, reporting a failure as the context's error (code -5)
-    int alloc(insitu_ctx* c, size_t count) {
-        const hipError_t e = try_alloc(count);
-        if (e == hipSuccess) return 0;
-        return fail(c, -5, std::string(Pinned ? "hipHostMalloc of " : "hipMalloc of ") + std::to_string(count * sizeof(T)) +
-                               " bytes failed: " + hipGetErrorString(e));
-    }
-    // grow-only: keeps what it holds when that is large enough
-    int reserve(insitu_ctx* c, size_t count) { return count <= n_ ? 0 : alloc(c, count); }
-
-private:
-    T* p_ = nullptr;
-    size_t n_ = 0;
-};
-template <typename T>
-using PinnedBuf = DevBuf<T, true>;
-
-struct Brick {
-    DevBuf<unsigned char> d;            // blocked layout with halo (insitu_sampling.h)
-    int dtype = -1;
-    int dims[3] = {0, 0, 0};
-    float im[16];
-    bool valid = false;
-};
-
 size_t dtype_size(int dt) { return dt == INSITU_U8 ? 1 : (dt == INSITU_U16 ? 2 : 4); }
 
-// float mat4 product with the same operation order as the shaders' `A * B` (and the oracle)
-void mat4_mul_f(const float* a, const float* b, float* out) {
-    float t[16];
-    for (int c = 0; c < 4; ++c) {
-        const float x = b[c * 4 + 0], y = b[c * 4 + 1], z = b[c * 4 + 2], w = b[c * 4 + 3];
-        for (int r = 0; r < 4; ++r)
-            t[c * 4 + r] = std::fmaf(a[12 + r], w, std::fmaf(a[8 + r], z, std::fmaf(a[4 + r], y, a[r] * x)));
-    }
-    std::memcpy(out, t, sizeof t);
-}
-
-// general 4x4 inverse in double, rounded to float (column-major in and out)
-bool mat4_inverse(const float* m, float* out) {
-    double a[4][8];
-    for (int r = 0; r < 4; ++r) {
-        for (int c = 0; c < 4; ++c) a[r][c] = (double)m[c * 4 + r];
-        for (int c = 0; c < 4; ++c) a[r][4 + c] = (r == c) ? 1.0 : 0.0;
-    }
-    for (int col = 0; col < 4; ++col) {
-        int piv = col;
-        for (int r = col + 1; r < 4; ++r)
-            if (std::fabs(a[r][col]) > std::fabs(a[piv][col])) piv = r;
-        if (a[piv][col] == 0.0) return false;
-        if (piv != col)
-            for (int c = 0; c < 8; ++c) std::swap(a[piv][c], a[col][c]);
-        const double inv = 1.0 / a[col][col];
-        for (int c = 0; c < 8; ++c) a[col][c] *= inv;
-        for (int r = 0; r < 4; ++r) {
-            if (r == col) continue;
-            const double f = a[r][col];
-            for (int c = 0; c < 8; ++c) a[r][c] -= f * a[col][c];
-        }
-    }
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c) out[c * 4 + r] = (float)a[r][4 + c];
-    return true;
-}
-
 }  // namespace
-
-struct insitu_local_group {
-    std::vector<insitu_ctx*> ranks;
-};
-
-// tuning knobs of the VDI generator (insitu_set_option; seeded from the environment at create)
-struct Tuning {
-    long long exact_search = 0;
-    long long search_depth = 0;
-    long long long_samples = 384;   // measured optimum
-    long long round_batch = 28;     // round 5: 28 vs 20, three A/Bs on one box each: search -0.1 to -0.2 ms
-    long long search_oversub = 6;   // measured: one brick per GPU (N=8) 12.2 -> 10.9 ms, N=1..4 unchanged
-    long long pipe_oversub = 3;     // pipelined frames (their search overlaps the next first pass): emulated N=8
-                                    // share 4.62 -> 4.18 ms/frame, N=4 6.11 -> 5.62, N=1..2 unchanged
-    long long pipe_search_rays = 2048;   // pipelined frames: queued rays per searching block (0: the full grid)
-    long long tile_order = 1;       // sampling tiles longest-first
-    long long super_tile = 1;       // ... by the longest ray of super-tiles of this many tiles per edge
-    long long regroup = 1;          // search: deeper tree groups for the rays left once the queue is drained
-    long long exact_tile_keys = 0;  // 1: tile keys from all 64 rays of a tile (0: 16 of them)
-};
-
-// hipEvents of a frame (FrameSlot::ev).  EvRenderStart..EvGatherEnd stay consecutive: the stage times of
-// insitu_get_stats are the spans ev[i], ev[i + 1] over them.
-enum FrameEvent {
-    EvRenderStart = 0,
-    EvRenderEnd,       // the send buffers are ready
-    EvExchangeEnd,
-    EvCompositeEnd,
-    EvGatherEnd,
-    EvSampleEnd,       // sample / search split
-    EvCompactStart,
-    EvPeerReadsDone,   // (local group) this rank's copies out of its peers' buffers are done -- recorded after its
-                       // exchange and its gather; a peer's next render/composite waits on it before rewriting them
-    EvCountsIn,        // exchange counts in
-    EvPayloadStart,
-    EvImageOnHost,     // the root's image copied to the host buffer of insitu_gather
-    EvSlotFree,        // (pipelined) the frame's completion is done: its slot may be rendered into again
-    EvCompactEnd,
-    EvSearchEnd,       // (pipelined) the next frame's sampling may start (trigger mode 0)
-    kFrameEvents
-};
-
-// The generator's per-frame buffers and the frame's camera, events and stage flags.  Pipelined frames
-// (insitu_frame_pipelined) render frame k+1 into one slot while frame k is composited from the other.  The stage
-// functions (render_frame .. gather_frame) and their helpers are handed the slot they work on and the stream(s)
-// they enqueue on; insitu_ctx::cur and ::alt only say which slot holds what (below).  Unpipelined contexts use
-// one slot (the other stays empty).
-struct FrameSlot {
-    DevBuf<float4> vcol_send;
-    DevBuf<float2> vdep_send;
-    DevBuf<uint32_t> octree;
-    DevBuf<uint8_t> passes;
-    DevBuf<uint16_t> seg_pending;       // per brick and pixel: supersegments awaiting vdi_finish_kernel
-    DevBuf<uint16_t> seg_steps;         // per sub-VDI entry: step count of a deferred colour
-    DevBuf<GenCounters> counters;       // cache cursor + search queue counters
-    DevBuf<PendingRay> queue;           // rays queued for the search kernel (B*W*H)
-    DevBuf<float> cache;                // per-sample raymarch cache (32-byte chunks of 4 samples)
-    uint32_t cache_chunks = 0;          // its size as the kernels take it (0 while a reallocation has failed)
-    // default-sized caches (insitu_ctx::cache_adaptive) grow to the measured demand: the frame's cursor (chunks
-    // asked for) is copied to pinned h_ctr at the end of every render, read after the next synchronisation
-    uint32_t cache_grow_to = 0;         // > cache_chunks: reallocate before the next render
-    bool cache_sized = false;           // the default cache was sized from a frame's measured demand
-    PinnedBuf<GenCounters> h_ctr;       // pinned copy of `counters` (valid after a synchronisation)
-    bool h_ctr_pending = false;         // h_ctr's copy was enqueued and not yet observed after a synchronisation
-    bool h_ctr_valid = false;           // h_ctr holds the last render's counters (observed after a synchronisation)
-    bool search_launched = false;       // a render ran the persistent search kernel (fault flag valid)
-    DevBuf<uint32_t> tile_keys;         // longest-tiles-first order: keys / ids (2 x B*tiles each)
-    DevBuf<uint32_t> tile_ids;
-    DevBuf<unsigned char> sort_tmp;     // hipcub temporary storage (insitu_ctx::sort_tmp_bytes)
-    float ipv[16] = {}, pv[16] = {}, view[16] = {};
-    bool rendered = false, composited = false;
-    bool exchanged = false;             // the compositor's input lists are complete (VDI set readable)
-    bool pipelined = false;   // rendered by insitu_frame_pipelined (compaction runs with the completion)
-    hipStream_t search_stream = nullptr;   // pipelined: the slot's search, finish and counter copy run here
-    int flag_index = 0;                    // the slot's index in insitu_ctx::slots; pipelined: its drain trigger
-                                           // is insitu_ctx::pipe_flag[flag_index]
-    unsigned long long flag_value = 0;     // the last value a search of this slot stores to that flag (0: none yet);
-                                           // the slot's frames are sequential, so each stores one more than the last
-    hipEvent_t ev[kFrameEvents] = {};      // (FrameEvent above)
-    bool ev_valid[kFrameEvents] = {};
-};
-
-// The bound VDI of insitu_view_bind / insitu_view_bind_host -- a snapshot in the view layout, with its generating
-// camera -- and the output of the last insitu_view_render.  Its buffers belong to no frame slot and its work
-// runs on a stream of its own, which is idle between calls (both calls block).
-struct ViewState {
-    DevBuf<float4> col;                 // the snapshot's buffers (grown by a larger bind) ...
-    DevBuf<float2> dep;
-    DevBuf<uint8_t> cnt, tmax;
-    ViewVdi vdi{};                      // ... as the kernels take them, with its dimensions (view_reserve)
-    float pv_g[16] = {};                // proj * view of the generating camera
-    bool bound = false;
-    DevBuf<float4> out_color;           // (out_h, out_w) rgba32f / rgba8 of the last render (grown by a larger one)
-    DevBuf<uint32_t> out_image;
-    int out_w = 0, out_h = 0;           // of the last render (0: none yet)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    float ms = 0.0f;                    // the last render's kernel
-    long long skip = 1;                 // INSITU_OPT_VIEW_SKIP
-    // the compact view layout: vdi.loc != null says the bound VDI has it
-    long long compact_next = 0;         // INSITU_OPT_VIEW_COMPACT: the layout the next bind takes
-    DevBuf<uint16_t> loc;               // a pixel's entries before it in its block (vdi.boff is pk_boff)
-    // the packed stream of the bound VDI (insitu_view_pack, insitu_view_bind_packed; vdi_pack.hip)
-    bool counted = false;               // pk_boff and pk_E describe the bound VDI (once per bind; view_reserve clears it)
-    unsigned long long pk_E = 0;        // its stored entries
-    DevBuf<uint32_t> pk_bstat;          // PackOffsets of the bound VDI, a block each (grown by a larger bind)
-    DevBuf<unsigned long long> pk_boff;
-    DevBuf<PackTotals> pk_totals;       // device; read back through h_totals (pinned)
-    PinnedBuf<PackTotals> h_totals;
-    DevBuf<unsigned char> pk_stage;     // the depth and colour sections on the device, kept across calls
-    float ms_pack = 0.0f;               // the last pack's or unpack's kernels
-    // the merged bind (INSITU_VIEW_MERGED, insitu_view_bind_host_set; vdi_view_merge.hip)
-    DevBuf<MergeTotals> mg_totals;      // device; read back through h_mg_totals (pinned)
-    PinnedBuf<MergeTotals> h_mg_totals;
-    long long overlaps = 0;             // of the bound VDI (0 for the single-VDI binds)
-    float ms_bind = 0.0f;               // the last bind's kernels
-};
-
-struct insitu_ctx {
-    insitu_config cfg{};
-    insitu_local_group* group = nullptr;   // in-process rank group (test transport), else RCCL
-    int W = 0, H = 0, S = 0, N = 1, rank = 0, B = 1, V = 1, mode = INSITU_MODE_VDI;
-    int BV = 1;   // sub-VDIs per rank: B, or 1 when the bricks are the volumes of one VDI (merge_bricks)
-    int strip_w = 0, strip_tiles = 0, rows = 0, ncx = 0, ncy = 0;
-    size_t blockE = 0;      // VDI entries per (strip, brick) block
-    size_t plainBlock = 0;  // pixels per (strip, brick) block in plain mode
-    size_t stripPx = 0;     // pixels of one composited strip
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    ncclComm_t comm = nullptr;
-    std::vector<Brick> bricks;
-    DevBuf<float> d_tf;
-    DevBuf<float> d_cmap;
-    int n_tf = 0, n_cm = 0;
-    float cmag = 1.0f;                  // TransferDesc::cmag of the current LUTs
-    float conv_scale = 1.0f, conv_offset = 0.0f;
-    DevBuf<float4> d_vcol_recv;
-    DevBuf<float2> d_vdep_recv;
-    DevBuf<uint32_t> d_pcol_send;
-    DevBuf<uint32_t> d_pdep_send;
-    DevBuf<uint32_t> d_pcol_recv;
-    DevBuf<uint32_t> d_pdep_recv;
-    DevBuf<uint32_t> d_strip;
-    DevBuf<uint32_t> d_gather;
-    DevBuf<uint32_t> d_image;
-    DevBuf<float4> d_ref_col;           // reference-layout staging for insitu_distribute_vdis: send | recv
-    DevBuf<float> d_ref_dep;
-    DevBuf<uint16_t> d_ref_cnt;         // per source strip [y][xl] counts of the host-buffer path's lists
-    bool lists_from_reference = false;  // the last composite input came through insitu_distribute_vdis
-    // variable-length exchange (N > 1, VDI mode): compact messages per destination
-    DevBuf<float4> d_ccol_send;         // [d] regions of B*blockE entries
-    DevBuf<float2> d_cdep_send;
-    DevBuf<uint8_t> d_meta_send;        // [d] regions of meta_bytes
-    DevBuf<uint8_t> d_meta_recv;        // [s]
-    DevBuf<uint32_t> d_cursor;          // [d] entries packed for d | [N + s] entries received from s
-    PinnedBuf<uint32_t> h_tot;          // pinned copy of d_cursor
-    size_t meta_bytes = 0;
-    bool camera_set = false;
-    DevBuf<unsigned char> d_staging;    // host-buffer brick uploads (kept: re-ingest every N frames)
-    bool cache_adaptive = false;        // a default-sized sample cache: the slots' caches grow (FrameSlot)
-    size_t cache_max_chunks = 0;        // growth limit (45 % of the HBM free at create, 2^32 chunks)
-    int num_cus = 256;
-    int search_blocks = 0;
-    int search_lanes = 0;               // resident lanes of the search grid for the LUT sizes below
-    int search_lanes_tf = -1, search_lanes_cm = -1;
-    Tuning tune;
-    DevBuf<unsigned long long> d_dbg;      // INSITU_DEBUG_RAYS: per-round search timing
-    size_t sort_tmp_bytes = 0;          // of the slots' hipcub temporary storage
-    size_t dbg_entries = 0;
-    std::string dbg_path;
-    bool dbg_pending = false;
-    long long last_exchange_bytes = 0, last_exchange_entries = 0;
-    bool composite_vdi = false;         // VDICompositor output instead of the RGBA flatten
-    int S_out = 0;
-    size_t cblockE = 0;                 // composited-VDI entries per strip block (S_out slots)
-    DevBuf<float4> d_cvdi_col;          // this rank's composited strip (non-root ranks)
-    DevBuf<float2> d_cvdi_dep;
-    DevBuf<float4> d_gvdi_col;          // root: gathered composited strips [rank][block]
-    DevBuf<float2> d_gvdi_dep;
-    bool gvdi_valid = false;            // root: a gather has filled them, from the frame of camera gvdi_pv
-    float gvdi_pv[16] = {};
-    DevBuf<uint16_t> d_cvdi_cnt;        // per pixel of this rank's composited strip: slots written (non-root ranks)
-    DevBuf<uint16_t> d_gvdi_cnt;        // root: the gathered counts [rank][y][x_local]
-    DevBuf<uint8_t> d_cpasses;          // compositor search passes of the strip
-    DevBuf<float4> d_cseq;              // VDICompositor merge cache (kCompEntryF4 float4 per entry)
-    DevBuf<unsigned long long> d_cseq_cursor;
-    PinnedBuf<unsigned long long> h_cseq_demand;   // pinned: the last composite's demand (entries), written
-                                                   // by an async copy; read only by cache_observe after a sync
-    bool cseq_pending = false;          // that copy is enqueued and not yet observed
-    unsigned long long cseq_demand = 0; // the demand observed after the last composite's synchronisation
-    unsigned long long cseq_cap = 0;    // capacity (entries)
-    unsigned long long cseq_max = 0;    // growth limit (entries): 20 % of the HBM free at create
-    // the frame slots: `cur` holds the completed frame (what the unpipelined stage calls and the readers work
-    // on) and is the slot the next pipelined frame renders into.  Cross-frame pipelining
-    // (insitu_frame_pipelined, DistributedVolumeRenderer.kt:530-542: the composite is one frame stale) fills
-    // the second one, `alt` -- the frame in flight -- and adds the sampling and completion streams and the
-    // trigger flags below
-    FrameSlot slots[2];
-    FrameSlot* cur = &slots[0];
-    FrameSlot* alt = &slots[1];
-    insitu_ctx() { slots[1].flag_index = 1; }
-    insitu_ctx(const insitu_ctx&) = delete;   // (cur and alt point into the context)
-    insitu_ctx& operator=(const insitu_ctx&) = delete;
-    bool pipe_ready = false;            // *alt allocated, streams created
-    bool pipe_inflight = false;         // *alt holds a rendered frame whose completion is pending
-    bool ingest_batch = false;          // re-ingests since the last render: ev_ingest0 marks their start
-    hipEvent_t ev_ingest0 = nullptr, ev_ingest = nullptr;   // the last batch of re-ingests (start, end)
-    hipEvent_t ev_gate = nullptr;       // pipelined: `stream`'s work so far, waited for by the next first pass
-    hipStream_t pipe_sample = nullptr;  // the first pass of every pipelined frame (low priority)
-    hipStream_t pipe_comp = nullptr;    // exchange, composite, gather of the frame one behind (high priority)
-    // search-drain triggers, one per slot (device memory, written at system scope): a slot's frames are
-    // sequential, so its flag only grows (FrameSlot::flag_value) -- two slots' searches may overlap and drain
-    // in either order
-    DevBuf<unsigned long long> pipe_flag;
-    long long pipe_frames = 0;          // frame index of the next pipelined render
-    int pipe_trigger = 2;               // 0: after the previous search; 1: at its queue drain; 2: none (default:
-                                        // the search keeps only the blocks its queue needs)
-    bool pipe_wait_value = true;        // hipStreamWaitValue64 works here (else mode 1 falls back to 0)
-    ViewState view;
-    std::string err;
-};
-
-namespace {
 
 int fail(insitu_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
@@ -375,12 +38,11 @@ int fail(insitu_ctx* c, int code, const std::string& msg) {
     return code;
 }
 
-#define HIPCHK(ctx, expr)                                                                          \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(ctx, -3, std::string(#expr " failed: ") + hipGetErrorString(e_));          \
-    } while (0)
+bool is_root(const insitu_ctx* c) { return c->rank == 0; }
+
+CompletedFrame completed_frame(const insitu_ctx* c) { return {*c->cur, c->pipe_inflight ? c->pipe_comp : c->stream}; }
+
+namespace {
 
 #define NCCLCHK(ctx, expr)                                                                         \
     do {                                                                                           \
@@ -416,18 +78,8 @@ void release(insitu_ctx* c) {
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
 }
 
-bool is_root(const insitu_ctx* c) { return c->rank == 0; }
-
 // the other frame slot becomes the current one
 void swap_slot(insitu_ctx* c) { std::swap(c->cur, c->alt); }
-
-// the completed frame's slot and the stream its readbacks run on: with a pipelined frame in flight the completion
-// stream (the context stream may be busy with work for the next frame, the completion stream holds nothing of it)
-struct CompletedFrame {
-    FrameSlot& f;
-    hipStream_t s;
-};
-CompletedFrame completed_frame(const insitu_ctx* c) { return {*c->cur, c->pipe_inflight ? c->pipe_comp : c->stream}; }
 
 // after a synchronisation of the stream of slot f's last render: its cache demand (h_ctr) decides whether a
 // default-sized cache grows before the slot's next render
@@ -454,8 +106,8 @@ hipError_t cache_realloc(FrameSlot& f, size_t chunks) {
     return e;
 }
 
-// after a synchronisation of the stream of slot f's last render: did a persistent kernel of that render hit its
-// wall-clock bound?
+}  // namespace
+
 int check_fault(insitu_ctx* c, FrameSlot& f) {
     cache_observe(c, f);   // (a pending copy of the frame's counters reached h_ctr: we are after a synchronisation)
     if (!f.counters || !f.search_launched) return 0;
@@ -465,6 +117,8 @@ int check_fault(insitu_ctx* c, FrameSlot& f) {
     if (fault) return fail(c, -6, "VDI search kernel exceeded its loop bound (internal error)");
     return 0;
 }
+
+namespace {
 
 // this rank's composited-VDI strip block (the root composites straight into its gather slot)
 float4* cvdi_col(const insitu_ctx* c) { return c->rank == 0 ? c->d_gvdi_col : c->d_cvdi_col; }
@@ -1903,538 +1557,6 @@ int insitu_read_region(insitu_ctx* c, int which, int slot, int x0, int x1, void*
     return 0;
 }
 
-namespace {
-
-// the view's stream and events (first bind)
-int view_stream(insitu_ctx* c) {
-    ViewState& v = c->view;
-    if (!v.stream) HIPCHK(c, hipStreamCreateWithFlags(&v.stream, hipStreamNonBlocking));
-    if (!v.ev0) HIPCHK(c, hipEventCreate(&v.ev0));
-    if (!v.ev1) HIPCHK(c, hipEventCreate(&v.ev1));
-    return 0;
-}
-
-// room for `entries` list entries of the VDI being bound
-int view_reserve_entries(insitu_ctx* c, size_t entries) {
-    ViewState& v = c->view;
-    int rc = 0;
-    if ((rc = v.col.reserve(c, entries)) || (rc = v.dep.reserve(c, entries))) return rc;
-    v.vdi.col = v.col; v.vdi.dep = v.dep;
-    return 0;
-}
-
-// ... and room for a VDI of (W, H, S) in the view layout this bind takes (INSITU_OPT_VIEW_COMPACT as it stands now;
-// the bound VDI keeps it).  Dense: everything.  Compact: the counts, the tile maxima and the offsets; the entries
-// are reserved once the counts are there and add up to E (view_compact_offsets).
-int view_reserve(insitu_ctx* c, int W, int H, int S) {
-    ViewState& v = c->view;
-    if (int rc = view_stream(c)) return rc;
-    v.bound = false;
-    v.counted = false;
-    v.vdi = ViewVdi{};
-    const bool compact = v.compact_next != 0;
-    ViewLayoutSize sz{};
-    if (compact ? !view_compact_size(W, H, S, 0, &sz) : !view_dense_size(W, H, S, &sz))
-        return fail(c, -1, "view bind: needs W, H > 0, at most 2^30 pixels and S in [1,255]");
-    int rc = 0;
-    if ((rc = v.cnt.reserve(c, (size_t)sz.px)) || (rc = v.tmax.reserve(c, (size_t)sz.tiles))) return rc;
-    if (compact) {
-        if ((rc = v.loc.reserve(c, (size_t)sz.px)) || (rc = v.pk_totals.reserve(c, 1)) ||
-            (rc = v.pk_bstat.reserve(c, (size_t)sz.nblocks)) || (rc = v.pk_boff.reserve(c, (size_t)sz.nblocks)))
-            return rc;
-        v.vdi.loc = v.loc; v.vdi.boff = v.pk_boff;
-    }
-    v.vdi.cnt = v.cnt; v.vdi.tmax = v.tmax;
-    v.vdi.W = W; v.vdi.H = H; v.vdi.S = S; v.vdi.tiles_x = (W + 7) / 8; v.vdi.tiles_y = (H + 7) / 8;
-    return compact ? 0 : view_reserve_entries(c, (size_t)sz.entries);
-}
-
-int pack_offsets(insitu_ctx* c, int check_E, unsigned long long expect_E, PackTotals* tot, float* ms, const char* who,
-                 bool timing_open = false);
-
-// The compact layout once its counts are on the device (after ev0 on the view's stream, which is what *ms counts
-// from): the offset passes -- boff, loc and E -- and room for the E entries (at least 1).  Blocks.  With check_E
-// the counts are a stream's: *tot tells the caller when they are to be rejected, and nothing is reserved then.
-int view_compact_offsets(insitu_ctx* c, int check_E, unsigned long long expect_E, PackTotals* tot, float* ms, const char* who) {
-    ViewState& v = c->view;
-    if (int rc = pack_offsets(c, check_E, expect_E, tot, ms, who, true)) return rc;
-    if (tot->bad) return check_E ? 0 : fail(c, -6, std::string(who) + ": a count of the VDI exceeds S (internal error)");
-    v.pk_E = tot->E;
-    v.counted = true;
-    return view_reserve_entries(c, tot->E > 0 ? (size_t)tot->E : 1);
-}
-
-// view_build_kernel over `src` on the view's stream (compact: the count pass, the offsets, the write pass); blocks
-// until the snapshot is built
-int view_build(insitu_ctx* c, const ViewSource& src, const float* pv_g, const char* who) {
-    ViewState& v = c->view;
-    float ms_index = 0.0f;
-    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-    hipError_t e = hipSuccess;
-    if (v.vdi.loc) {
-        e = launch_view_build_count(src, v.vdi, v.stream);
-        if (e != hipSuccess) return fail(c, -3, std::string(who) + ": view_build_count_kernel: " + hipGetErrorString(e));
-        PackTotals tot{};
-        if (int rc = view_compact_offsets(c, 0, 0, &tot, &ms_index, who)) return rc;
-        HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-        e = launch_view_build_fill(src, v.vdi, v.stream);
-    } else {
-        e = launch_view_build(src, v.vdi, v.stream);
-    }
-    if (e == hipSuccess) e = hipEventRecord(v.ev1, v.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(v.stream);
-    if (e != hipSuccess) return fail(c, -3, std::string(who) + ": view_build_kernel: " + hipGetErrorString(e));
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_bind = ms_index + ms;
-    std::memcpy(v.pv_g, pv_g, sizeof v.pv_g);
-    v.overlaps = 0;
-    v.bound = true;
-    return 0;
-}
-
-// After one of the two merge kernels' launches (e) on the view's stream, behind ev0: the totals on the host; blocks.
-// *ms = the kernel's HIP-event time.
-int view_merge_done(insitu_ctx* c, hipError_t e, const char* who, const char* kernel, MergeTotals* tot, float* ms) {
-    ViewState& v = c->view;
-    if (e != hipSuccess) return fail(c, -3, std::string(who) + ": " + kernel + ": " + hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(v.ev1, v.stream));
-    HIPCHK(c, hipMemcpyAsync(v.h_mg_totals, v.mg_totals, sizeof(MergeTotals), hipMemcpyDeviceToHost, v.stream));
-    HIPCHK(c, hipStreamSynchronize(v.stream));
-    *tot = *v.h_mg_totals;
-    *ms = 0.0f;
-    (void)hipEventElapsedTime(ms, v.ev0, v.ev1);
-    return 0;
-}
-
-// The merged bind: the src.n lists per pixel of a (W, H) window of S-slot lists, merged by start
-// depth into a VDI of S_m = max(1, the longest merged list) slots.  More than 255 is rejected and leaves no VDI
-// bound.  Blocks until the snapshot is built.
-int view_merge(insitu_ctx* c, const ViewSource& src, int W, int H, int S, const float* pv_g, const char* who) {
-    ViewState& v = c->view;
-    v.bound = false;
-    v.counted = false;
-    if (int rc = view_stream(c)) return rc;
-    if (int rc = v.mg_totals.reserve(c, 1)) return rc;
-    if (!v.h_mg_totals) HIPCHK(c, v.h_mg_totals.try_alloc(1));
-    MergeTotals tot{};
-    float ms_count = 0.0f, ms_merge = 0.0f, ms_index = 0.0f;
-    // compact: the count pass leaves every pixel's merged length as its count (the slots are known after it)
-    const bool compact = v.compact_next != 0;
-    if (compact)
-        if (int rc = view_reserve(c, W, H, 1)) return rc;
-    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-    if (int rc = view_merge_done(c, launch_view_merge_count(src, W, H, S, v.mg_totals, compact ? v.vdi.cnt : nullptr, v.stream),
-                                 who, "view_merge_count_kernel", &tot, &ms_count))
-        return rc;
-    if (tot.max_count > 255u)
-        return fail(c, -1, std::string(who) + ": the merged lists hold up to " + std::to_string(tot.max_count) +
-                               " entries per pixel, at most 255 can be bound");
-    const int Sm = tot.max_count > 0u ? (int)tot.max_count : 1;
-    if (compact) {
-        v.vdi.S = Sm;
-        PackTotals ptot{};
-        HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-        if (int rc = view_compact_offsets(c, 0, 0, &ptot, &ms_index, who)) return rc;
-    } else if (int rc = view_reserve(c, W, H, Sm)) {
-        return rc;
-    }
-    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-    if (int rc = view_merge_done(c, launch_view_merge(src, S, v.vdi, v.mg_totals, v.stream), who, "view_merge_kernel", &tot,
-                                 &ms_merge))
-        return rc;
-    v.ms_bind = ms_count + ms_index + ms_merge;
-    v.overlaps = (long long)tot.overlaps;
-    std::memcpy(v.pv_g, pv_g, sizeof v.pv_g);
-    v.bound = true;
-    return 0;
-}
-
-}  // namespace
-
-int insitu_view_bind(insitu_ctx* c, int source, int slot) {
-    if (!c) return fail(nullptr, -1, "insitu_view_bind: null context");
-    if (source == INSITU_VIEW_MERGED) {   // (a failed merged bind leaves no VDI bound)
-        c->view.bound = false;
-        c->view.counted = false;
-    }
-    if (c->mode != INSITU_MODE_VDI) return fail(c, -1, "insitu_view_bind: VDI mode only");
-    auto [f, st] = completed_frame(c);
-    ViewSource src{};
-    src.n = 1;
-    const float* pv = nullptr;
-    int S = 0;
-    if (source == INSITU_VIEW_GATHERED) {
-        if (!c->composite_vdi) return fail(c, -1, "insitu_view_bind: the gathered VDI needs a composite_vdi context");
-        if (!is_root(c)) return fail(c, -1, "insitu_view_bind: the gathered VDI is on rank 0 only");
-        if (!c->gvdi_valid) return fail(c, -1, "insitu_view_bind: no frame gathered yet");
-        src.col = c->d_gvdi_col; src.dep = c->d_gvdi_dep; src.cnt = c->d_gvdi_cnt;
-        src.cnt_stride = 0; src.cnt_dstride = c->stripPx; src.cnt_pitch = (size_t)c->strip_w;
-        src.B = 1; src.b = 0;
-        S = c->S_out;
-        pv = c->gvdi_pv;
-    } else if (source == INSITU_VIEW_BRICK || source == INSITU_VIEW_MERGED) {
-        if (source == INSITU_VIEW_MERGED && slot != 0)
-            return fail(c, -1, "insitu_view_bind: INSITU_VIEW_MERGED takes slot 0 (it binds every sub-VDI of the rank)");
-        if (slot < 0 || slot >= c->BV) return fail(c, -1, "insitu_view_bind: slot out of range");
-        if (!f.rendered || !f.ev_valid[EvRenderEnd]) return fail(c, -1, "insitu_view_bind: no frame rendered yet");
-        src.col = f.vcol_send; src.dep = f.vdep_send; src.cnt = f.seg_pending;
-        src.cnt_stride = (size_t)c->W * (size_t)c->H; src.cnt_dstride = (size_t)c->strip_w; src.cnt_pitch = (size_t)c->W;
-        src.B = c->BV; src.b = slot;
-        if (source == INSITU_VIEW_MERGED) src.n = c->BV;   // slots 0..BV-1: the whole window
-        S = c->S;
-        pv = f.pv;
-    } else {
-        return fail(c, -1, "insitu_view_bind: unknown source " + std::to_string(source));
-    }
-    src.strip_w = c->strip_w; src.strip_tiles = c->strip_tiles;
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    // the frame's own work is done before the snapshot is taken (its render may still be running when no
-    // stage after it has synchronised)
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (f.search_stream) HIPCHK(c, hipStreamSynchronize(f.search_stream));
-    if (int rc = check_fault(c, f)) return rc;
-    // (a set of one list is that list: bound with its own S slots, as INSITU_VIEW_BRICK binds it)
-    if (src.n > 1) return view_merge(c, src, c->W, c->H, S, pv, "insitu_view_bind");
-    if (int rc = view_reserve(c, c->W, c->H, S)) return rc;
-    return view_build(c, src, pv, "insitu_view_bind");
-}
-
-namespace {
-
-// n dense VDIs in the reference layout, staged on the device and bound: one as it is (view_build_kernel, S slots),
-// several merged (view_merge)
-int view_bind_host_lists(insitu_ctx* c, const char* who, const void* const* colors, const void* const* depths, int n,
-                         int W, int H, int S, const insitu_camera* gen_cam) {
-    if (W <= 0 || H <= 0 || S < 1 || S > 255) return fail(c, -1, std::string(who) + ": needs W, H > 0 and S in [1,255]");
-    float pv[16];
-    mat4_mul_f(gen_cam->proj, gen_cam->view, pv);
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (n == 1) {
-        if (int rc = view_reserve(c, W, H, S)) return rc;
-    } else if (int rc = view_stream(c)) {
-        return rc;
-    }
-    const size_t E = (size_t)W * (size_t)H * (size_t)S;
-    DevBuf<float4> rc_;   // (the staging pair is freed at scope exit: the view's stream is idle by then)
-    DevBuf<float2> rd_;
-    HIPCHK(c, rc_.try_alloc(E * (size_t)n));
-    if (rd_.try_alloc(E * (size_t)n) != hipSuccess) return fail(c, -5, std::string(who) + ": staging allocation failed");
-    hipError_t e = hipSuccess;
-    for (int j = 0; j < n && e == hipSuccess; ++j) {
-        e = hipMemcpyAsync(rc_ + E * (size_t)j, colors[j], E * sizeof(float4), hipMemcpyHostToDevice, c->view.stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(rd_ + E * (size_t)j, depths[j], E * sizeof(float2), hipMemcpyHostToDevice, c->view.stream);
-    }
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(c->view.stream);
-        return fail(c, -3, std::string(who) + ": upload: " + hipGetErrorString(e));
-    }
-    ViewSource src{};
-    src.col = rc_;
-    src.dep = rd_;
-    src.reference = 1;
-    src.ref_stride = E;
-    src.n = n;
-    // (both block: the staging is free afterwards)
-    if (n == 1) return view_build(c, src, pv, who);
-    return view_merge(c, src, W, H, S, pv, who);
-}
-
-}  // namespace
-
-int insitu_view_bind_host(insitu_ctx* c, const void* color, const void* depth, int W, int H, int S,
-                          const insitu_camera* gen_cam) {
-    if (!c) return fail(nullptr, -1, "insitu_view_bind_host: null context");
-    if (!color || !depth || !gen_cam) return fail(c, -1, "insitu_view_bind_host: null argument");
-    return view_bind_host_lists(c, "insitu_view_bind_host", &color, &depth, 1, W, H, S, gen_cam);
-}
-
-int insitu_view_bind_host_set(insitu_ctx* c, const void* const* colors, const void* const* depths, int n, int W, int H,
-                              int S, const insitu_camera* gen_cam) {
-    const char* who = "insitu_view_bind_host_set";
-    if (!c) return fail(nullptr, -1, std::string(who) + ": null context");
-    c->view.bound = false;   // (a failed bind leaves no VDI bound)
-    c->view.counted = false;
-    if (!colors || !depths || !gen_cam) return fail(c, -1, std::string(who) + ": null argument");
-    if (n < 1 || n > kMaxLists)
-        return fail(c, -1, std::string(who) + ": " + std::to_string(n) + " VDIs, needs 1 to " + std::to_string(kMaxLists));
-    for (int j = 0; j < n; ++j)
-        if (!colors[j] || !depths[j]) return fail(c, -1, std::string(who) + ": null VDI " + std::to_string(j));
-    return view_bind_host_lists(c, who, colors, depths, n, W, H, S, gen_cam);
-}
-
-// ---- the packed stream of the bound VDI (vdi_pack.hip, vdi_pack_format.h) ----
-namespace {
-
-// the offset buffers for the bound dimensions, the totals and their pinned copy; the offset passes
-// (pack_count_kernel, pack_scan_kernel) over the view's counts on the view's stream.  Blocks; *tot = what they
-// found, *ms = their HIP-event time (timing_open: from the ev0 the caller has recorded, with its own pass over the
-// counts behind it).  A compact VDI in the making gets its loc with them.
-int pack_offsets(insitu_ctx* c, int check_E, unsigned long long expect_E, PackTotals* tot, float* ms, const char* who,
-                 bool timing_open) {
-    ViewState& v = c->view;
-    const uint64_t px = (uint64_t)v.vdi.W * (uint64_t)v.vdi.H;
-    if (px > kPackMaxPixels) return fail(c, -1, std::string(who) + ": more than 2^30 pixels");
-    const size_t blocks = (size_t)((px + (uint64_t)kPackBlockPx - 1) / (uint64_t)kPackBlockPx);
-    int rc = 0;
-    if ((rc = v.pk_totals.reserve(c, 1)) || (rc = v.pk_bstat.reserve(c, blocks)) || (rc = v.pk_boff.reserve(c, blocks)))
-        return rc;
-    if (!v.h_totals) HIPCHK(c, v.h_totals.try_alloc(1));
-    const PackOffsets o{v.vdi.cnt, v.pk_bstat, v.pk_boff, v.pk_totals, (uint32_t)px, (uint32_t)blocks,
-                        v.vdi.loc ? v.loc.get() : nullptr};
-    if (!timing_open) HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-    hipError_t e = launch_pack_offsets(o, v.vdi.S, check_E, expect_E, v.stream);
-    if (e != hipSuccess) return fail(c, -3, std::string(who) + ": pack_count_kernel: " + hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(v.ev1, v.stream));
-    HIPCHK(c, hipMemcpyAsync(v.h_totals, v.pk_totals, sizeof(PackTotals), hipMemcpyDeviceToHost, v.stream));
-    HIPCHK(c, hipStreamSynchronize(v.stream));
-    *tot = *v.h_totals;
-    *ms = 0.0f;
-    (void)hipEventElapsedTime(ms, v.ev0, v.ev1);
-    return 0;
-}
-
-// E and the block offsets of the bound VDI: counted once per bind
-int pack_count_bound(insitu_ctx* c, float* ms, const char* who) {
-    ViewState& v = c->view;
-    *ms = 0.0f;
-    if (v.counted) return 0;
-    PackTotals tot{};
-    if (int rc = pack_offsets(c, 0, 0, &tot, ms, who)) return rc;
-    if (tot.bad) return fail(c, -6, std::string(who) + ": a count of the bound VDI exceeds S (internal error)");
-    v.pk_E = tot.E;
-    v.counted = true;
-    return 0;
-}
-
-// room for the two sections on the device: depth at 0, colour at the next multiple of 16 (*colour_at)
-int pack_stage_reserve(insitu_ctx* c, const PackLayout& lay, size_t* colour_at) {
-    ViewState& v = c->view;
-    *colour_at = (lay.depth_bytes + 15) & ~(size_t)15;
-    return v.pk_stage.reserve(c, *colour_at + lay.colour_bytes);
-}
-
-bool pack_format_ok(int format) { return format == INSITU_PACK_FLOAT || format == INSITU_PACK_HALF; }
-
-}  // namespace
-
-size_t insitu_view_pack_bytes(insitu_ctx* c, int format) {
-    const char* err = nullptr;
-    PackLayout lay{};
-    float ms = 0.0f;
-    if (!c) err = "null context";
-    else if (!pack_format_ok(format)) err = "bad format";
-    else if (!c->view.bound) err = "no VDI bound (insitu_view_bind first)";
-    else if (hipSetDevice(c->cfg.device) != hipSuccess) err = "hipSetDevice failed";
-    else if (pack_count_bound(c, &ms, "insitu_view_pack_bytes")) return 0;   // (its message stands)
-    else if (!pack_layout((uint32_t)format, (uint32_t)c->view.vdi.W, (uint32_t)c->view.vdi.H, (uint32_t)c->view.vdi.S,
-                          c->view.pk_E, &lay)) err = "the stream's size does not fit";
-    if (err) {
-        fail(c, -1, std::string("insitu_view_pack_bytes: ") + err);
-        return 0;
-    }
-    return lay.total;
-}
-
-int insitu_view_pack(insitu_ctx* c, int format, void* host_out, size_t cap, size_t* bytes) {
-    if (!c) return fail(nullptr, -1, "insitu_view_pack: null context");
-    ViewState& v = c->view;
-    if (!pack_format_ok(format)) return fail(c, -1, "insitu_view_pack: bad format " + std::to_string(format));
-    if (!v.bound) return fail(c, -1, "insitu_view_pack: no VDI bound (insitu_view_bind first)");
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    float ms_count = 0.0f;
-    if (int rc = pack_count_bound(c, &ms_count, "insitu_view_pack")) return rc;
-    PackHeader h{};
-    h.format = (uint32_t)format; h.W = (uint32_t)v.vdi.W; h.H = (uint32_t)v.vdi.H; h.S = (uint32_t)v.vdi.S;
-    h.E = v.pk_E;
-    std::memcpy(h.pv_g, v.pv_g, sizeof h.pv_g);
-    PackLayout lay{};
-    if (!pack_layout(h.format, h.W, h.H, h.S, h.E, &lay)) return fail(c, -1, "insitu_view_pack: the stream's size does not fit");
-    if (bytes) *bytes = lay.total;
-    if (!host_out || cap < lay.total)
-        return fail(c, -1, "insitu_view_pack: output buffer too small (" + std::to_string(lay.total) + " bytes needed)");
-    if (v.vdi.loc) {
-        // compact: the bound VDI's arrays are the sections (FLOAT: three copies and no kernel, so ms_pack is 0;
-        // HALF: the colours converted element by element)
-        unsigned char* out = static_cast<unsigned char*>(host_out);
-        const bool half = format == INSITU_PACK_HALF;
-        if (half && h.E > 0)
-            if (int rc = v.pk_stage.reserve(c, lay.colour_bytes)) return rc;
-        HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-        if (half && h.E > 0) {
-            hipError_t e = launch_pack_convert(v.vdi.col, v.pk_stage, h.E, 1, v.stream);
-            if (e != hipSuccess) return fail(c, -3, std::string("pack_convert_kernel: ") + hipGetErrorString(e));
-        }
-        HIPCHK(c, hipEventRecord(v.ev1, v.stream));
-        HIPCHK(c, hipMemcpyAsync(out + kPackHeaderBytes, v.vdi.cnt, (size_t)lay.px, hipMemcpyDeviceToHost, v.stream));
-        if (h.E > 0) {
-            HIPCHK(c, hipMemcpyAsync(out + lay.depth_off, v.vdi.dep, lay.depth_bytes, hipMemcpyDeviceToHost, v.stream));
-            HIPCHK(c, hipMemcpyAsync(out + lay.colour_off, half ? (const void*)v.pk_stage.get() : (const void*)v.vdi.col,
-                                     lay.colour_bytes, hipMemcpyDeviceToHost, v.stream));
-        }
-        HIPCHK(c, hipStreamSynchronize(v.stream));
-        pack_write_header(out, h);
-        std::memset(out + kPackHeaderBytes + (size_t)lay.px, 0, lay.depth_off - kPackHeaderBytes - (size_t)lay.px);
-        float ms = 0.0f;
-        v.ms_pack = (half && h.E > 0 && hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) ? ms_count + ms : ms_count;
-        return 0;
-    }
-    size_t colour_at = 0;
-    if (int rc = pack_stage_reserve(c, lay, &colour_at)) return rc;
-    PackParams p{};
-    p.vdi = v.vdi;
-    p.boff = v.pk_boff;
-    p.dep = reinterpret_cast<float2*>(v.pk_stage.get());
-    p.col = v.pk_stage + colour_at;
-    p.half = format == INSITU_PACK_HALF ? 1 : 0;
-    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-    hipError_t e = launch_vdi_pack(p, v.stream);
-    if (e != hipSuccess) return fail(c, -3, std::string("vdi_pack_kernel: ") + hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(v.ev1, v.stream));
-    unsigned char* out = static_cast<unsigned char*>(host_out);
-    HIPCHK(c, hipMemcpyAsync(out + kPackHeaderBytes, v.vdi.cnt, (size_t)lay.px, hipMemcpyDeviceToHost, v.stream));
-    if (h.E > 0) {
-        HIPCHK(c, hipMemcpyAsync(out + lay.depth_off, v.pk_stage, lay.depth_bytes, hipMemcpyDeviceToHost, v.stream));
-        HIPCHK(c, hipMemcpyAsync(out + lay.colour_off, v.pk_stage + colour_at, lay.colour_bytes, hipMemcpyDeviceToHost, v.stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(v.stream));
-    pack_write_header(out, h);
-    std::memset(out + kPackHeaderBytes + (size_t)lay.px, 0, lay.depth_off - kPackHeaderBytes - (size_t)lay.px);
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_pack = ms_count + ms;
-    return 0;
-}
-
-int insitu_view_bind_packed(insitu_ctx* c, const void* data, size_t bytes) {
-    if (!c) return fail(nullptr, -1, "insitu_view_bind_packed: null context");
-    ViewState& v = c->view;
-    v.bound = false;   // (a rejected stream leaves no VDI bound)
-    v.counted = false;
-    PackHeader h{};
-    PackLayout lay{};
-    if (const char* why = pack_parse(data, bytes, &h, &lay))
-        return fail(c, -1, std::string("insitu_view_bind_packed: stream rejected: ") + why);
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (int rc = view_reserve(c, (int)h.W, (int)h.H, (int)h.S)) return rc;
-    const unsigned char* in = static_cast<const unsigned char*>(data);
-    if (v.vdi.loc) {
-        // compact: the counts, validated by the offset passes as below before anything depends on them; then the
-        // sections are the layout's arrays -- copied as they are, the HALF colours widened element by element
-        HIPCHK(c, hipMemcpyAsync(v.vdi.cnt, in + kPackHeaderBytes, (size_t)lay.px, hipMemcpyHostToDevice, v.stream));
-        PackTotals tot{};
-        float ms_count = 0.0f;
-        HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-        if (int rc = view_compact_offsets(c, 1, h.E, &tot, &ms_count, "insitu_view_bind_packed")) return rc;
-        if (tot.bad) {
-            if (tot.max_count > h.S)
-                return fail(c, -1, "insitu_view_bind_packed: stream rejected: a count of " + std::to_string(tot.max_count) +
-                                       " exceeds S = " + std::to_string(h.S));
-            return fail(c, -1, "insitu_view_bind_packed: stream rejected: the counts add up to " + std::to_string(tot.E) +
-                                   ", the header says " + std::to_string(h.E));
-        }
-        const bool half = h.format == kPackHalf;
-        if (half && h.E > 0)
-            if (int rc = v.pk_stage.reserve(c, lay.colour_bytes)) return rc;
-        if (h.E > 0) {
-            HIPCHK(c, hipMemcpyAsync(v.vdi.dep, in + lay.depth_off, lay.depth_bytes, hipMemcpyHostToDevice, v.stream));
-            HIPCHK(c, hipMemcpyAsync(half ? (void*)v.pk_stage.get() : (void*)v.vdi.col, in + lay.colour_off, lay.colour_bytes,
-                                     hipMemcpyHostToDevice, v.stream));
-        }
-        HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-        hipError_t e = half ? launch_pack_convert(v.pk_stage, v.vdi.col, h.E, 0, v.stream) : hipSuccess;
-        if (e == hipSuccess) e = launch_view_tmax(v.vdi, v.stream);
-        if (e != hipSuccess) return fail(c, -3, std::string("pack_convert_kernel: ") + hipGetErrorString(e));
-        HIPCHK(c, hipEventRecord(v.ev1, v.stream));
-        HIPCHK(c, hipStreamSynchronize(v.stream));
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_pack = v.ms_bind = ms_count + ms;
-        std::memcpy(v.pv_g, h.pv_g, sizeof v.pv_g);
-        v.overlaps = 0;
-        v.bound = true;
-        return 0;
-    }
-    size_t colour_at = 0;
-    if (int rc = pack_stage_reserve(c, lay, &colour_at)) return rc;
-    // the counts go straight into the view layout; nothing reads them as counts until they have been checked
-    HIPCHK(c, hipMemcpyAsync(v.vdi.cnt, in + kPackHeaderBytes, (size_t)lay.px, hipMemcpyHostToDevice, v.stream));
-    if (h.E > 0) {
-        HIPCHK(c, hipMemcpyAsync(v.pk_stage, in + lay.depth_off, lay.depth_bytes, hipMemcpyHostToDevice, v.stream));
-        HIPCHK(c, hipMemcpyAsync(v.pk_stage + colour_at, in + lay.colour_off, lay.colour_bytes, hipMemcpyHostToDevice, v.stream));
-    }
-    // validated on the device before anything is scattered: every count <= S, and the counts add up to E
-    PackTotals tot{};
-    float ms_count = 0.0f;
-    if (int rc = pack_offsets(c, 1, h.E, &tot, &ms_count, "insitu_view_bind_packed")) return rc;
-    if (tot.bad) {
-        if (tot.max_count > h.S)
-            return fail(c, -1, "insitu_view_bind_packed: stream rejected: a count of " + std::to_string(tot.max_count) +
-                                   " exceeds S = " + std::to_string(h.S));
-        return fail(c, -1, "insitu_view_bind_packed: stream rejected: the counts add up to " + std::to_string(tot.E) +
-                               ", the header says " + std::to_string(h.E));
-    }
-    PackParams p{};
-    p.vdi = v.vdi;
-    p.boff = v.pk_boff;
-    p.dep = reinterpret_cast<float2*>(v.pk_stage.get());
-    p.col = v.pk_stage + colour_at;
-    p.half = h.format == kPackHalf ? 1 : 0;
-    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-    hipError_t e = launch_vdi_unpack(p, v.stream);
-    if (e != hipSuccess) return fail(c, -3, std::string("vdi_unpack_kernel: ") + hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(v.ev1, v.stream));
-    HIPCHK(c, hipStreamSynchronize(v.stream));
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms_pack = v.ms_bind = ms_count + ms;
-    std::memcpy(v.pv_g, h.pv_g, sizeof v.pv_g);
-    v.overlaps = 0;
-    v.pk_E = h.E;
-    v.counted = true;
-    v.bound = true;
-    return 0;
-}
-
-int insitu_view_render(insitu_ctx* c, const insitu_camera* cam, int out_w, int out_h, void* host_out, size_t cap) {
-    if (!c) return fail(nullptr, -1, "insitu_view_render: null context");
-    if (!cam) return fail(c, -1, "insitu_view_render: null camera");
-    ViewState& v = c->view;
-    if (!v.bound) return fail(c, -1, "insitu_view_render: no VDI bound (insitu_view_bind first)");
-    if (out_w <= 0 || out_h <= 0 || (long long)out_w * (long long)out_h > (1ll << 30))
-        return fail(c, -1, "insitu_view_render: bad output size");
-    const size_t px = (size_t)out_w * (size_t)out_h;
-    if (host_out && cap < px * 4) return fail(c, -1, "insitu_view_render: output buffer too small");
-    ViewParams p{};
-    float iv[16], ip[16];
-    if (cam->has_inverses) {
-        std::memcpy(iv, cam->inv_view, sizeof iv);
-        std::memcpy(ip, cam->inv_proj, sizeof ip);
-    } else if (!mat4_inverse(cam->view, iv) || !mat4_inverse(cam->proj, ip)) {
-        return fail(c, -1, "insitu_view_render: view or projection matrix is singular");
-    }
-    mat4_mul_f(iv, ip, p.ipv_n);
-    std::memcpy(p.pv_g, v.pv_g, sizeof p.pv_g);
-    HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (px > v.out_color.count() || px > v.out_image.count()) {
-        v.out_w = v.out_h = 0;   // (nothing to read until this render is done)
-        int rc = 0;
-        if ((rc = v.out_color.reserve(c, px)) || (rc = v.out_image.reserve(c, px))) return rc;
-    }
-    p.vdi = v.vdi;
-    p.out_w = out_w; p.out_h = out_h;
-    p.skip = (int)v.skip;
-    p.out_color = v.out_color;
-    p.out_image = v.out_image;
-    HIPCHK(c, hipEventRecord(v.ev0, v.stream));
-    hipError_t e = launch_vdi_view(p, v.stream);
-    if (e != hipSuccess) return fail(c, -3, std::string("vdi_view_kernel: ") + hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(v.ev1, v.stream));
-    if (host_out) HIPCHK(c, hipMemcpyAsync(host_out, v.out_image, px * 4, hipMemcpyDeviceToHost, v.stream));
-    HIPCHK(c, hipStreamSynchronize(v.stream));
-    v.out_w = out_w; v.out_h = out_h;
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, v.ev0, v.ev1) == hipSuccess) v.ms = ms;
-    return 0;
-}
-
 int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
     if (!c || !out) return fail(c, -1, "insitu_get_stats: null argument");
     const CompletedFrame done = completed_frame(c);
@@ -2485,22 +1607,7 @@ int insitu_get_stats(insitu_ctx* c, insitu_stats* out) {
     if (hipEventQuery(c->ev_ingest) == hipSuccess && hipEventElapsedTime(&ms, c->ev_ingest0, c->ev_ingest) == hipSuccess)
         out->ms_ingest = ms;
     (void)hipGetLastError();
-    out->ms_view = c->view.ms;
-    out->ms_pack = c->view.ms_pack;
-    out->view_slots = c->view.bound ? c->view.vdi.S : 0;
-    out->view_overlaps = c->view.bound ? c->view.overlaps : 0;
-    out->ms_view_bind = c->view.ms_bind;
-    if (c->view.bound) {
-        ViewState& v = c->view;
-        float ms_count = 0.0f;   // (a dense bind counts its entries when they are first asked for)
-        if (int rc = pack_count_bound(c, &ms_count, "insitu_get_stats")) return rc;
-        ViewLayoutSize sz{};
-        const bool ok = v.vdi.loc ? view_compact_size(v.vdi.W, v.vdi.H, v.vdi.S, v.pk_E, &sz)
-                                  : view_dense_size(v.vdi.W, v.vdi.H, v.vdi.S, &sz);
-        out->view_entries = (long long)v.pk_E;
-        out->view_bytes = ok ? (long long)sz.bytes : 0;
-        out->view_compact = v.vdi.loc ? 1 : 0;
-    }
+    if (int rc = view_stats(c, out)) return rc;
     out->ms_sample = out->ms_render;
     float a = 0.0f, b = 0.0f;
     if (c->mode == INSITU_MODE_VDI && f.ev_valid[EvRenderEnd] && span(EvRenderStart, EvSampleEnd, &a) &&

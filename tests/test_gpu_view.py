@@ -19,16 +19,13 @@ import view_binding as vb
 from insitu_amd import native, scene
 from insitu_amd.renderer import InSituContext, LocalGroup
 from scenes import make_scene
+from view_binding import bits as _bits, fails as _fails
 
 pytestmark = pytest.mark.gpu
 
 W, H, S, S_OUT = vb.VDI_W, vb.VDI_H, vb.VDI_S, 4
 CAMS = vb.view_cameras()
 G = vb.gen_camera()
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _scenes():
@@ -167,12 +164,6 @@ def test_snapshot_survives_pipelined_frames():
         assert ctx.pipeline_flush()[0] == 3
 
 
-def _fails(ctx, rc, text):
-    assert rc == -1
-    msg = ctx.lib.insitu_last_error(ctx.h).decode()
-    assert text in msg, msg
-
-
 def test_error_paths(brick):
     lib = brick.ctx.lib
     cam = CAMS["yaw20"].native()
@@ -184,13 +175,16 @@ def test_error_paths(brick):
         _fails(ctx, lib.insitu_view_bind(ctx.h, 7, 0), "unknown source")
     ctx = brick.ctx
     _fails(ctx, lib.insitu_view_bind(ctx.h, native.VIEW_BRICK, 1), "slot out of range")
+    _fails(ctx, lib.insitu_view_render(ctx.h, ctypes.byref(cam), 50, 37, out.ctypes.data, out.nbytes), "no VDI bound")
     _fails(ctx, lib.insitu_view_bind(ctx.h, native.VIEW_BRICK, -1), "slot out of range")
-    ctx.view_bind(native.VIEW_BRICK, 0)   # (a failed bind leaves nothing bound: bind again for the later tests)
+    _fails(ctx, lib.insitu_view_render(ctx.h, ctypes.byref(cam), 50, 37, out.ctypes.data, out.nbytes), "no VDI bound")
+    ctx.view_bind(native.VIEW_BRICK, 0)   # (a failed bind leaves no VDI bound: bind again for the later tests)
     _fails(ctx, lib.insitu_view_render(ctx.h, ctypes.byref(cam), 50, 37, out.ctypes.data, out.nbytes - 1), "too small")
     _fails(ctx, lib.insitu_view_render(ctx.h, ctypes.byref(cam), 0, 37, out.ctypes.data, out.nbytes), "output size")
     _fails(ctx, lib.insitu_view_render(ctx.h, ctypes.byref(cam), 50, -3, out.ctypes.data, out.nbytes), "output size")
     _fails(ctx, lib.insitu_view_bind_host(ctx.h, brick.col.ctypes.data, brick.dep.ctypes.data, W, H, 0,
                                           ctypes.byref(G.native())), "S in [1,255]")
+    _fails(ctx, lib.insitu_view_render(ctx.h, ctypes.byref(cam), 50, 37, out.ctypes.data, out.nbytes), "no VDI bound")
     ctx.view_bind(native.VIEW_BRICK, 0)
     # the gathered VDI lives on rank 0 only
     group = LocalGroup(2)

@@ -19,9 +19,9 @@ from insitu_amd import native
 from insitu_amd.renderer import InSituContext
 from insitu_amd.vdi_io import PACK_FLOAT, PACK_HALF, pack_vdi, unpack_vdi
 from scenes import make_scene
-from test_gpu_view_merge import _random_set
 from test_vdi_pack import empty_vdi, random_vdi, rejected_streams
 from test_view_merge import loop_merge, scene_set
+from view_binding import bits as _bits, fails as _fails, random_set as _random_set, read_all as _read_all, set_bricks as _set_bricks
 
 pytestmark = pytest.mark.gpu
 
@@ -33,16 +33,6 @@ SIZE = vb.OUT_SIZES[1]
 VIEWS = (("yaw90", SIZE), ("yaw180", SIZE), ("cross", SIZE), ("same", (128, 96)))
 FORMATS = (PACK_FLOAT, PACK_HALF)
 COMPACT = native.OPT_VIEW_COMPACT
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _fails(ctx, rc, text):
-    assert rc == -1
-    msg = ctx.lib.insitu_last_error(ctx.h).decode()
-    assert text in msg, msg
 
 
 def _header(stream):
@@ -120,17 +110,6 @@ def _dense_and_compact(ctx, bind, what, vdi=None, cams=None, merged=False, visib
             assert compact["stats"][key] == dense["stats"][key], key
     assert compact["stats"]["view_entries"] == dense["stats"]["view_entries"]
     return dense, compact
-
-
-def _set_bricks(ctx, scenes):
-    sc = scenes[0]
-    ctx.set_transfer(sc["tf"], sc["cmap"], sc["conv_scale"], sc["conv_offset"])
-    for b, s in enumerate(scenes):
-        ctx.set_brick(b, s["vol"], s["model"])
-
-
-def _read_all(ctx, n):
-    return ([ctx.read(native.BUF_VDI_COLOR, b) for b in range(n)], [ctx.read(native.BUF_VDI_DEPTH, b) for b in range(n)])
 
 
 @pytest.fixture(scope="module")

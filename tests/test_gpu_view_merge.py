@@ -18,6 +18,7 @@ from insitu_amd import native, scene
 from insitu_amd.renderer import InSituContext, LocalGroup
 from insitu_amd.vdi_io import PACK_FLOAT, pack_vdi
 from test_view_merge import loop_merge, scene_set
+from view_binding import bits as _bits, fails as _fails, random_set as _random_set, read_all as _read_all, set_bricks as _set_bricks
 
 pytestmark = pytest.mark.gpu
 
@@ -27,31 +28,10 @@ G = vb.gen_camera()
 SIZE = vb.OUT_SIZES[1]
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _fails(ctx, rc, text):
-    assert rc == -1
-    msg = ctx.lib.insitu_last_error(ctx.h).decode()
-    assert text in msg, msg
-
-
 def _nothing_bound(ctx):
     cam = CAMS["yaw20"].native()
     img = np.empty((37, 50, 4), np.uint8)
     _fails(ctx, ctx.lib.insitu_view_render(ctx.h, ctypes.byref(cam), 50, 37, img.ctypes.data, img.nbytes), "no VDI bound")
-
-
-def _set_bricks(ctx, scenes, first=0):
-    sc = scenes[0]
-    ctx.set_transfer(sc["tf"], sc["cmap"], sc["conv_scale"], sc["conv_offset"])
-    for b, s in enumerate(scenes):
-        ctx.set_brick(first + b, s["vol"], s["model"])
-
-
-def _read_all(ctx, n):
-    return ([ctx.read(native.BUF_VDI_COLOR, b) for b in range(n)], [ctx.read(native.BUF_VDI_DEPTH, b) for b in range(n)])
 
 
 def _assert_packed(ctx, merged, gen, what):
@@ -172,27 +152,6 @@ def test_ragged_window():
         assert np.count_nonzero(counts[48:]) >= 20 and np.count_nonzero(counts[:, 32:]) >= 20   # (oracle: 54 and 130)
         _assert_packed(ctx, m.merged, cam, "ragged window")
         assert m.stats["view_slots"] == m.merged[0].shape[2] and m.stats["view_overlaps"] == m.merged[2]
-
-
-def _random_set(n, seed, w=16, h=8, s=2):
-    """n VDIs of 16x8, S = 2: list lengths 0..2, start depths drawn from 24 shared values (so lists tie), sorted
-    inside a list, every entry as long as half a step of those values."""
-    rng = np.random.default_rng(seed)
-    grid = np.linspace(0.9, 0.99, 24).astype(np.float32)
-    half = np.float32(0.5) * (grid[1] - grid[0])
-    cols, deps = [], []
-    for _ in range(n):
-        pick = np.sort(rng.integers(0, 12, size=(w, h, s)) * 2 + np.arange(s), axis=2)   # distinct, increasing
-        start = grid[pick]
-        counts = rng.integers(0, s + 1, size=(w, h))
-        live = np.arange(s)[None, None, :] < counts[:, :, None]
-        dep = np.zeros((w, h, 2 * s), np.float32)
-        dep[:, :, 0::2] = start * live
-        dep[:, :, 1::2] = (start + half) * live
-        col = rng.random(size=(w, h, s, 4), dtype=np.float32) * live[..., None]
-        cols.append(col.astype(np.float32))
-        deps.append(dep)
-    return cols, deps
 
 
 @pytest.mark.parametrize("n", [3, 9, 32])

@@ -19,6 +19,7 @@ from insitu_amd.renderer import InSituContext
 from insitu_amd.vdi_io import PACK_FLOAT, PACK_HALF, pack_vdi, unpack_vdi
 from scenes import make_scene
 from test_vdi_pack import empty_vdi, random_vdi, rejected_streams
+from view_binding import bits as _bits, fails as _fails
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +31,6 @@ SIZE = vb.OUT_SIZES[1]
 # far cameras at 50x37, and the generating camera at twice the VDI's resolution (rays in cell planes)
 VIEWS = (("yaw90", SIZE), ("yaw180", SIZE), ("cross", SIZE), ("same", (128, 96)))
 FORMATS = (PACK_FLOAT, PACK_HALF)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _scenes():
@@ -247,12 +244,6 @@ def test_rebinding_grows_and_reuses_buffers(brick):
         brick.ctx.view_bind(native.VIEW_BRICK, 0)             # (as the fixture left it)
     _assert_same_views(_views(brick.ctx), brick.views(), "device bind after the smaller packed VDI")
     assert np.array_equal(brick.ctx.view_pack(PACK_FLOAT), big)
-
-
-def _fails(ctx, rc, text):
-    assert rc == -1
-    msg = ctx.lib.insitu_last_error(ctx.h).decode()
-    assert text in msg, msg
 
 
 def test_error_paths(brick):

@@ -14,7 +14,7 @@ from pathlib import Path
 import numpy as np
 
 import oracle_binding as orc
-from insitu_amd import scene
+from insitu_amd import native, scene
 
 ROOT = Path(__file__).resolve().parent.parent
 SRC = ROOT / "tests" / "view_ref" / "view_ref.c"
@@ -226,3 +226,46 @@ def on_outer_plane(gen_cam, cam, out_w: int, out_h: int, W: int, H: int, tol: fl
         for P in planes:
             out |= (np.abs(ndc[0][..., axis] - P) <= tol) & (np.abs(ndc[1][..., axis] - P) <= tol)
     return out
+
+
+# ---- shared by the GPU tests of the view subsystem (tests/test_gpu_view*.py) ----
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def fails(ctx, rc, text):
+    assert rc == -1
+    msg = ctx.lib.insitu_last_error(ctx.h).decode()
+    assert text in msg, msg
+
+
+def set_bricks(ctx, scenes, first=0):
+    sc = scenes[0]
+    ctx.set_transfer(sc["tf"], sc["cmap"], sc["conv_scale"], sc["conv_offset"])
+    for b, s in enumerate(scenes):
+        ctx.set_brick(first + b, s["vol"], s["model"])
+
+
+def read_all(ctx, n):
+    return ([ctx.read(native.BUF_VDI_COLOR, b) for b in range(n)], [ctx.read(native.BUF_VDI_DEPTH, b) for b in range(n)])
+
+
+def random_set(n, seed, w=16, h=8, s=2):
+    """n VDIs of 16x8, S = 2: list lengths 0..2, start depths drawn from 24 shared values (so lists tie), sorted
+    inside a list, every entry as long as half a step of those values."""
+    rng = np.random.default_rng(seed)
+    grid = np.linspace(0.9, 0.99, 24).astype(np.float32)
+    half = np.float32(0.5) * (grid[1] - grid[0])
+    cols, deps = [], []
+    for _ in range(n):
+        pick = np.sort(rng.integers(0, 12, size=(w, h, s)) * 2 + np.arange(s), axis=2)   # distinct, increasing
+        start = grid[pick]
+        counts = rng.integers(0, s + 1, size=(w, h))
+        live = np.arange(s)[None, None, :] < counts[:, :, None]
+        dep = np.zeros((w, h, 2 * s), np.float32)
+        dep[:, :, 0::2] = start * live
+        dep[:, :, 1::2] = (start + half) * live
+        col = rng.random(size=(w, h, s, 4), dtype=np.float32) * live[..., None]
+        cols.append(col.astype(np.float32))
+        deps.append(dep)
+    return cols, deps
