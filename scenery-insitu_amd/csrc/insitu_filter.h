@@ -28,7 +28,8 @@ namespace insitu {
 //     m = c (1.4e-5 sqrt(est) + 5e-11 c) + 1e-6 est,
 // i.e. relative to the difference itself (1.4e-7 at diff^2 = 1e-4), not to the colour range: near
 // small thresholds the estimate almost always decides.  Written supersegments always take the
-// exact adjusted colour.  tests/test_gpu_parity.py checks filtered == exact on whole frames.
+// exact adjusted colour.  tests/test_gpu_parity.py checks filtered == exact on whole frames (at c = 2), and
+// tests/test_gpu_inputs.py filtered == oracle == exact for c from 1 to inf (other colour maps and alphas).
 //
 // c is a constant of the transfer function (TransferDesc::cmag, computed by the host): with C the
 // largest |rgb| component of the colour map and A the largest |alpha| of the TF, every sample colour

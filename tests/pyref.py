@@ -189,7 +189,8 @@ class Volume:
 
     @staticmethod
     def _pair(t, n):
-        fl = math.floor(t) if t == t else math.nan
+        # floorf: NaN and +-inf are their own floor (inf - inf then makes the fraction NaN)
+        fl = float(math.floor(t)) if math.isfinite(t) else t
         frac = sub(t, fl) if fl == fl else math.nan
         if not (fl >= -1.0):
             fl = -1.0

@@ -160,3 +160,56 @@ def test_golden_fixture_oracle(name):
         rc, rd = orc.plain_raycast(inp, dim0, dim1)
         assert np.array_equal(rc, g["color"])
         assert np.array_equal(rd, g["depth"])
+
+
+# ---- inputs off the default scene (tests/scenes.py variants): the GPU parity tests of test_gpu_inputs.py are only
+# as good as the oracle on these, so pyref pins it there too
+
+def _oracle_frame(sc, W, H, S):
+    inp = orc.Inputs(sc["vol"], sc["im"], sc["tf"], sc["cmap"], sc["conv_k"], sc["conv_offset"], sc["cam"])
+    return orc.vdi_generate(inp, W, H, S)
+
+
+@pytest.mark.parametrize("name", ["opaque", "out_of_range", "conv_wide", "cam_inside", "field_f32_nonfinite", "hdr"])
+def test_vdi_generate_pyref_equals_oracle_on_variants(name):
+    """Alpha exactly 1 (log2(0) = -inf), alpha outside [0, 1], LUT coordinates outside the table, a ray that
+    starts inside the brick, NaN / +inf / -inf voxels and colours far above 1: the independent Python
+    restatement and the C oracle agree bit for bit."""
+    from scenes import variant_scene
+    W, H, S = 16, 12, 4
+    sc = variant_scene(name, W, H, n=16)
+    V, cam = _pyref_inputs(sc)
+    pc, pd, po, pp = pyref.vdi_image(V, cam, W, H, S)
+    rc, rd, ro, rp = _oracle_frame(sc, W, H, S)
+    assert np.count_nonzero(rd) > 0 and rp.max() > 2
+    assert np.all(np.isfinite(rc)) and np.all(np.isfinite(rd))
+    assert np.array_equal(_u32(pc), rc.view(np.uint32))
+    assert np.array_equal(_u32(pd), rd.view(np.uint32))
+    assert np.array_equal(np.asarray(po, np.uint32), ro)
+    assert np.array_equal(np.asarray(pp, np.int32), rp)
+
+
+@pytest.mark.parametrize("name", ["opaque", "field_f32_nonfinite"])
+def test_plain_pyref_equals_oracle_on_variants(name):
+    from scenes import variant_scene
+    dim = 20
+    sc = variant_scene(name, dim, dim, n=16)
+    V, cam = _pyref_inputs(sc)
+    inp = orc.Inputs(sc["vol"], sc["im"], sc["tf"], sc["cmap"], sc["conv_k"], sc["conv_offset"], sc["cam"])
+    rc, rd = orc.plain_raycast(inp, dim, dim)
+    for gy in range(dim):
+        for gx in range(dim):
+            c, d = pyref.plain_pixel(V, cam, gx, gy, dim, dim)
+            assert c == rc[gy, gx].tolist() and d == rd[gy, gx].tolist(), (gx, gy)
+    assert np.count_nonzero(rc[..., 3]) > 0
+
+
+def test_input_variants_do_what_they_claim():
+    """Every named variant, through the oracle at the GPU tests' size: the inputs leave the table / reach alpha 1 /
+    start inside the brick / ... as their names say, the searching ones search, and the oracle terminates."""
+    import scenes
+    W, H, S = 64, 48, 8
+    for name in ("base",) + scenes.ALL_VARIANTS:
+        for dtype in ("u16", "u8") if name in scenes.CONV_VARIANTS else ("u16",):
+            sc = scenes.variant_scene(name, W, H, dtype=dtype)
+            scenes.check_variant_claims(name, sc, _oracle_frame(sc, W, H, S), lambda s: _oracle_frame(s, W, H, S))
