@@ -15,6 +15,8 @@ result with a single-rank context that renders every brick itself (bit for bit):
   pipe     : pipelined frames (insitu_frame_pipelined, three cameras + the flush): each completed frame's
              image equals the single-rank frame of its camera (the exchange runs in the next frame's call)
   pipe_cvdi: the same through the VDICompositor (gathered composited VDI of every frame)
+Optional arguments W H set the window (default 64 48: strips of whole 8x8 tiles); 50 37 on 2 ranks gives
+25-pixel strips with a partial tile column inside the image and, in plain mode (a W x W texture), 25-row strips.
 When the ranks outnumber the GPUs (a one-GPU box), each rank announces a distinct NCCL host id so
 that RCCL accepts two ranks on one device and connects them through its socket transport on the
 loopback interface: the same library code paths, a slower wire.
@@ -45,7 +47,8 @@ from scenes import gray_scott_u16  # noqa: E402
 dev = int(os.environ.get("LOCAL_RANK", "0")) % max(1, torch.cuda.device_count())
 torch.cuda.set_device(dev)
 dist.init_process_group("gloo")
-W, H, S = 64, 48, 6
+W, H = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) >= 3 else (64, 48)
+S = 6
 NB = 8 if world == 8 else 4   # bricks (virtual ranks): 2x2x1, or 2x2x2 for the 8-way decomposition
 vol = gray_scott_u16(32)
 bricks = [(np.roll(vol, 5 * i, axis=1).copy(),

@@ -38,6 +38,31 @@ def make_scene(n=32, W=64, H=48, yaw=30.0, pitch=20.0, samples_per_voxel=1.0, dt
                 conv_offset=conv_offset, conv_k=conv_k, W=W, H=H)
 
 
+# ---------------------------------------------------------------- the N-rank strip scene
+# The bricks of the multi-rank group tests seen from close by (radius 2.0: at the default 3.5 the outer strips
+# of a window are empty), shared by the CPU pin (test_compositor_oracle.py) and the GPU strip tests
+# (test_gpu_strips.py).  nb == 4: 2 x 2 x 1 unit bricks at z = -0.5 (Gray-Scott seeds 11..14); nb > 4: the
+# first nb of 2 x 2 x 2 bricks, the second z layer re-using the four fields rolled by 5 voxels along y.
+
+STRIP_S = 6
+
+
+def strip_bricks(nb: int) -> list:
+    """nb bricks as make_scene dicts (vol, model, im, tf, cmap, conv_*), 24^3 voxels each."""
+    out = []
+    for i in range(nb):
+        origin = (-1.0 + (i % 2), -1.0 + (i // 2), -0.5) if nb == 4 else (-1.0 + (i % 2), -1.0 + (i // 2) % 2, -1.0 + (i // 4))
+        b = make_scene(n=24, seed=11 + i % 4, origin=origin)
+        if i >= 4:
+            b["vol"] = np.roll(b["vol"], 5, axis=1).copy()
+        out.append(b)
+    return out
+
+
+def strip_camera(W: int, H: int, yaw: float = 35.0, pitch: float = 20.0):
+    return scene.orbit_camera(W, H, radius=2.0, yaw_deg=yaw, pitch_deg=pitch, voxel_world=1.0 / 24)
+
+
 # ---------------------------------------------------------------- inputs off the one scene
 # Named variants of make_scene(n=32, yaw=40): each changes ONE input of the base scene (transfer function,
 # colour map, conversion, camera, model matrix or field) and returns the same dict, so the CPU pins

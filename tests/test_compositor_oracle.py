@@ -91,3 +91,29 @@ def test_composite_merges_in_depth_order():
     in_min = np.where(in_starts != 0, in_starts, np.inf).min(axis=2)
     has = np.isfinite(in_min)
     assert np.array_equal(starts[..., 0][has], in_min[has].astype(np.float32))
+
+
+@pytest.mark.parametrize("W,H,strips,nb", [(60, 37, 4, 4), (40, 37, 8, 8)])
+def test_strip_composite_equals_cropped_whole(W, H, strips, nb):
+    """orc_vdi_composite and orc_vdi_flatten over one strip's columns (x_offset = r * strip_w) equal the
+    whole-width result cropped to that strip, bit for bit, on strips that are not whole tiles (15 and 5 pixels
+    of the N-rank strip scene, scenes.strip_bricks): the whole-frame and the per-strip references of
+    test_gpu_strips.py are interchangeable."""
+    from scenes import STRIP_S, strip_bricks, strip_camera
+    S_out = 4
+    cam = strip_camera(W, H)
+    subs = [orc.vdi_generate(orc.Inputs(b["vol"], b["im"], b["tf"], b["cmap"], b["conv_k"], b["conv_offset"], cam),
+                             W, H, STRIP_S) for b in strip_bricks(nb)]
+    colors, depths = [s[0] for s in subs], [s[1] for s in subs]
+    ipv = orc.ipv_of(cam)
+    wc, wd, wp = orc.vdi_composite(colors, depths, W, H, 0, W, ipv, S_out)
+    wimg = orc.vdi_flatten(colors, depths, W, H, 0, W, ipv)
+    sw = W // strips
+    for r in range(strips):
+        x0, x1 = r * sw, (r + 1) * sw
+        c, d, p = orc.vdi_composite(colors, depths, W, H, x0, sw, ipv, S_out)
+        assert np.array_equal(c.view(np.uint32), wc[x0:x1].view(np.uint32)), r
+        assert np.array_equal(d.view(np.uint32), wd[x0:x1].view(np.uint32)), r
+        assert np.array_equal(p, wp[:, x0:x1]), r
+        assert np.array_equal(orc.vdi_flatten(colors, depths, W, H, x0, sw, ipv), wimg[:, x0:x1]), r
+        assert np.count_nonzero(d) > 0 and np.count_nonzero(wimg[:, x0:x1, 3]) > 0, f"strip {r} is empty"

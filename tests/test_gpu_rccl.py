@@ -48,6 +48,20 @@ def test_rccl_exchange_composite_gather(world):
 
 
 @pytest.mark.timeout(300)
+def test_rccl_ragged_strips():
+    """The same cases on 2 ranks at 50x37: 25-pixel strips, so a partial tile column lies inside the image, and
+    in plain mode 25-row strips of a 50x50 texture.  This reaches what the in-process group cannot: the
+    pipelined completion path (the compact pack on the completion stream) and the host-buffer path
+    (distributeVDIs from reference-layout strips) off the 8-grid."""
+    p = _run(2, [str(ROOT / "tests" / "rccl_worker.py"), "50", "37"], timeout=280)
+    out = p.stdout + p.stderr
+    assert p.returncode == 0 and "RCCL_OK" in p.stdout, p.stdout[-6000:] + "\n--- stderr ---\n" + p.stderr[:6000]
+    assert out.count("== 1-rank result: True") == 5, out[-4000:]
+    assert out.count("pipelined frames == 1-rank frames: True") == 2, out[-4000:]
+    assert "image == oracle (4 bricks): True" in out, out[-4000:]
+
+
+@pytest.mark.timeout(300)
 @pytest.mark.parametrize("launch", ["torchrun", "self"])
 def test_bench_two_ranks(launch):
     """bench.py --gpus 2 (reduced bricks): the multi-rank path runs, launched by torch.distributed.run
