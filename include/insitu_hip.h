@@ -291,7 +291,7 @@ int insitu_read_region(insitu_ctx* ctx, int which, int slot, int x0, int x1, voi
  * S_m = max(1, the longest merged list) slots (insitu_stats.view_slots); more than 255 is rejected with -1.
  * With one sub-VDI (one brick, merge_bricks) it is INSITU_VIEW_BRICK of slot 0; with nranks > 1 it merges the
  * rank's own bricks only.
- * A failed insitu_view_bind* call leaves no VDI bound -- whichever of the four it is, and wherever it fails. */
+ * A failed insitu_view_bind* call leaves no VDI bound -- whichever of them it is, and wherever it fails. */
 int insitu_view_bind(insitu_ctx* ctx, int source, int slot);
 /* The same from host memory: a VDI in the reference layout -- colour (W,H,S,4) rgba32f and depth (W,H,2S) r32f, x
  * slowest, as the dumps hold it (vdi_io.read_vdi) -- with the camera that generated it.  W, H and S (1..255) need
@@ -330,6 +330,20 @@ int insitu_view_pack(insitu_ctx* ctx, int format, void* host_out, size_t cap, si
  * anything is placed by them; a rejected stream returns -1.  The receiving end of
  * VolumeFromFileExample.kt:907-1030 (the remote viewer's upload of the message). */
 int insitu_view_bind_packed(insitu_ctx* ctx, const void* data, size_t bytes);
+/* Bind n (1..32) packed streams of one window and one generating camera as one merged VDI (an addition within ABI
+ * 12: no existing call or structure changes).  streams[j] of bytes[j] bytes takes the place of slot j of
+ * INSITU_VIEW_MERGED: the lists of a pixel are merged by start depth, the lowest stream first on a tie, entries
+ * copied bit for bit, into S_m = max(1, the longest merged list) slots; more than 255 is rejected with -1.  Stream
+ * j's list at a pixel is its first `count` entries, ending before the first one whose start depth is 0, so the call
+ * binds what insitu_view_bind_host_set binds of the streams unpacked (vdi_io.unpack_vdi) and zero-padded to the
+ * largest S -- without ever expanding them: the merge reads the streams' sections as they arrive (DESIGN.md section
+ * 9.8).  W, H and pv_g (its 64 bytes) must agree across the set; S and the format may differ, a binary16 colour is
+ * widened exactly.  Every stream is checked as insitu_view_bind_packed checks one, header and size on the host
+ * before anything is allocated, counts on the device before any entry is read; a rejection returns -1 and names
+ * the stream's index and the reason, and no VDI is left bound.  n = 1 is insitu_view_bind_packed of that stream.
+ * Runs on the view's own stream: legal while a pipelined frame is in flight.  insitu_stats reports it through
+ * view_slots, view_overlaps, view_entries, view_bytes, view_compact and ms_view_bind. */
+int insitu_view_bind_packed_set(insitu_ctx* ctx, const void* const* streams, const size_t* bytes, int n);
 int insitu_get_stats(insitu_ctx* ctx, insitu_stats* out);
 /* Set a tuning option (enum insitu_option) for the following renders; -1 on an unknown option or
  * a value out of range.  Environment variables INSITU_<OPTION NAME> (INSITU_EXACT_SEARCH,

@@ -243,6 +243,10 @@ struct ViewState {
     PinnedBuf<MergeTotals> h_mg_totals;
     long long overlaps = 0;             // of the bound VDI (0 for the single-VDI binds)
     float ms_bind = 0.0f;               // the last bind's kernels
+    // a set of packed streams (insitu_view_bind_packed_set), kept across calls and grown by a larger set
+    DevBuf<unsigned char> ps_stage;     // every stream's counts, depth section and colour section, as they arrive
+    DevBuf<unsigned char> ps_index;     // the PackedStream table, the streams' totals, and each stream's own boff, bstat, loc
+    PinnedBuf<PackTotals> h_ps_totals;  // kMaxLists: the totals of all streams, read back in one copy
 };
 
 struct insitu_ctx {

@@ -395,4 +395,30 @@ hipError_t launch_vdi_unpack(const PackParams& p, hipStream_t s);
 hipError_t launch_pack_convert(const void* src, void* dst, unsigned long long n, int to_half, hipStream_t s);
 hipError_t launch_view_tmax(const ViewVdi& v, hipStream_t s);   // v.tmax from v.cnt
 
+// ---- a set of packed streams merged into the bound VDI (insitu_view_bind_packed_set) ----
+// One stream of the set as it lies staged on the device: its counts with their own offsets (off: boff and loc as a
+// compact ViewVdi has them, so entry k of pixel p is entry off.boff[p >> 8] + off.loc[p] + k of dep and col), the
+// header's S and E that the offset passes check the counts against, and whether col holds 4 x binary16 per entry.
+struct PackedStream {
+    PackOffsets off;
+    const float2* dep;
+    const void* col;
+    unsigned long long E;
+    uint32_t S, half;
+};
+// The offset passes over every stream of the set at once (px counts and nblocks blocks each): stream j's boff,
+// loc and totals, bad as launch_pack_offsets sets it with check_E.  `set` is device memory.
+hipError_t launch_pack_offsets_set(const PackedStream* set, int n, uint32_t px, uint32_t nblocks, hipStream_t s);
+
+// What the merge kernels read in place of a ViewSource: list j of pixel (x, y) is stream j's list of pixel y*W + x,
+// its first min(count, S_j) entries.  `streams` is device memory (a lane picks its stream by a computed index).
+struct PackedSource {
+    const PackedStream* streams;
+    int n, W;
+};
+// as the ViewSource forms above (S is not looked at: every stream has its own)
+hipError_t launch_view_merge_count(const PackedSource& src, int W, int H, int S, MergeTotals* tot, uint8_t* cnt,
+                                   hipStream_t s);
+hipError_t launch_view_merge(const PackedSource& src, int S, const ViewVdi& dst, MergeTotals* tot, hipStream_t s);
+
 }  // namespace insitu

@@ -157,14 +157,15 @@ int view_build(insitu_ctx* c, const ViewSource& src, int S, const float* pv_g, c
 
 // The merged bind: the src.n lists per pixel of the reserved index's window, S slots each, merged by
 // start depth into a VDI of S_m = max(1, the longest merged list) slots.  More than 255 is rejected.  Blocks until
-// the snapshot is built.
-int view_merge(insitu_ctx* c, const ViewSource& src, int S, const float* pv_g, const char* who) {
+// the snapshot is built.  SRC: ViewSource, or PackedSource (a set of packed streams, whose offset passes took ms0).
+template <class SRC>
+int view_merge(insitu_ctx* c, const SRC& src, int S, const float* pv_g, const char* who, float ms0 = 0.0f) {
     ViewState& v = c->view;
     if (int rc = v.mg_totals.reserve(c, 1)) return rc;
     if (!v.h_mg_totals) HIPCHK(c, v.h_mg_totals.try_alloc(1));
     const CopyOut totals{v.h_mg_totals.get(), v.mg_totals.get(), sizeof(MergeTotals)};
     const bool compact = v.vdi.loc != nullptr;
-    float ms = 0.0f;
+    float ms = ms0;
     // compact: the count pass leaves every pixel's merged length as its count (the slots are known after it)
     const auto count = [&]() -> Launched {
         return {launch_view_merge_count(src, v.vdi.W, v.vdi.H, S, v.mg_totals, compact ? v.vdi.cnt : nullptr, v.stream),
@@ -404,15 +405,23 @@ int insitu_view_pack(insitu_ctx* c, int format, void* host_out, size_t cap, size
     return 0;
 }
 
-int insitu_view_bind_packed(insitu_ctx* c, const void* data, size_t bytes) {
-    const char* who = "insitu_view_bind_packed";
-    if (!c) return fail(nullptr, -1, "insitu_view_bind_packed: null context");
+namespace {
+
+// what a rejected stream's message begins with: `who`, and in a set the stream's index
+std::string pack_rejected(const char* who, int index) {
+    return std::string(who) + (index < 0 ? ": stream rejected: " : ": stream " + std::to_string(index) + " rejected: ");
+}
+std::string pack_bad_counts(const PackTotals& tot, const PackHeader& h) {
+    if (tot.max_count > h.S) return "a count of " + std::to_string(tot.max_count) + " exceeds S = " + std::to_string(h.S);
+    return "the counts add up to " + std::to_string(tot.E) + ", the header says " + std::to_string(h.E);
+}
+
+// one packed stream into the view layout (insitu_view_bind_packed; a set of one); index: see pack_rejected
+int view_bind_packed_one(insitu_ctx* c, const char* who, int index, const void* data, size_t bytes) {
     ViewState& v = c->view;
-    view_unbind(v);
     PackHeader h{};
     PackLayout lay{};
-    if (const char* why = pack_parse(data, bytes, &h, &lay))
-        return fail(c, -1, std::string("insitu_view_bind_packed: stream rejected: ") + why);
+    if (const char* why = pack_parse(data, bytes, &h, &lay)) return fail(c, -1, pack_rejected(who, index) + why);
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (int rc = view_reserve_index(c, (int)h.W, (int)h.H)) return rc;
     const unsigned char* in = static_cast<const unsigned char*>(data);
@@ -422,13 +431,7 @@ int insitu_view_bind_packed(insitu_ctx* c, const void* data, size_t bytes) {
     PackTotals tot{};
     float ms = 0.0f;
     if (int rc = view_count(c, who, (int)h.S, 1, h.E, &tot, &ms, no_launch)) return rc;
-    if (tot.bad) {
-        if (tot.max_count > h.S)
-            return fail(c, -1, "insitu_view_bind_packed: stream rejected: a count of " + std::to_string(tot.max_count) +
-                                   " exceeds S = " + std::to_string(h.S));
-        return fail(c, -1, "insitu_view_bind_packed: stream rejected: the counts add up to " + std::to_string(tot.E) +
-                               ", the header says " + std::to_string(h.E));
-    }
+    if (tot.bad) return fail(c, -1, pack_rejected(who, index) + pack_bad_counts(tot, h));
     const bool half = h.format == kPackHalf;
     PackSections s{};
     if (int rc = view_reserve_entries(c, (int)h.S, h.E)) return rc;
@@ -440,6 +443,85 @@ int insitu_view_bind_packed(insitu_ctx* c, const void* data, size_t bytes) {
     if (int rc = view_timed(c, who, &ms, [&] { return pack_launch(v, s, half, h.E, false); })) return rc;
     view_commit(v, h.pv_g, ms, &tot, 0, true);
     return 0;
+}
+
+}  // namespace
+
+int insitu_view_bind_packed(insitu_ctx* c, const void* data, size_t bytes) {
+    if (!c) return fail(nullptr, -1, "insitu_view_bind_packed: null context");
+    view_unbind(c->view);
+    return view_bind_packed_one(c, "insitu_view_bind_packed", -1, data, bytes);
+}
+
+// n packed streams of one window and one generating camera, merged per pixel straight from their sections (DESIGN.md
+// section 9.8): staged as they arrive, each with an index of its own (boff, loc: the offset passes over its counts,
+// which also validate them), read by the merge kernels as a PackedSource.  No stream is expanded to S-slot lists.
+int insitu_view_bind_packed_set(insitu_ctx* c, const void* const* streams, const size_t* bytes, int n) {
+    const char* who = "insitu_view_bind_packed_set";
+    static_assert(kPackSetMax == kMaxLists, "a set holds as many streams as the merge takes lists");
+    if (!c) return fail(nullptr, -1, std::string(who) + ": null context");
+    ViewState& v = c->view;
+    view_unbind(v);
+    if (!streams || !bytes) return fail(c, -1, std::string(who) + ": null argument");
+    if (n < 1 || n > kMaxLists)
+        return fail(c, -1, std::string(who) + ": " + std::to_string(n) + " streams, needs 1 to " + std::to_string(kMaxLists));
+    if (n == 1) return view_bind_packed_one(c, who, 0, streams[0], bytes[0]);
+    PackHeader h[kPackSetMax];
+    PackLayout lay[kPackSetMax];
+    PackSetStage at[kPackSetMax];
+    int index = -1;
+    if (const char* why = pack_set_parse(streams, bytes, n, h, lay, &index))
+        return fail(c, -1, index < 0 ? std::string(who) + ": " + why : pack_rejected(who, index) + why);
+    size_t stage_bytes = 0;
+    if (!pack_set_stage(lay, n, at, &stage_bytes)) return fail(c, -1, std::string(who) + ": the streams' size does not fit");
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = view_reserve_index(c, (int)h[0].W, (int)h[0].H)) return rc;
+    // the index of the streams, apart from the bound VDI's: table | totals | per stream boff | bstat | loc
+    const size_t px = (size_t)lay[0].px, nb = (size_t)view_blocks((uint64_t)px), N = (size_t)n;
+    const size_t totals_at = (N * sizeof(PackedStream) + 15) & ~(size_t)15;
+    const size_t boff_at = totals_at + N * sizeof(PackTotals);
+    const size_t bstat_at = boff_at + N * nb * sizeof(unsigned long long);
+    const size_t loc_at = (bstat_at + N * nb * sizeof(uint32_t) + 15) & ~(size_t)15;
+    int rc = 0;
+    if ((rc = v.ps_index.reserve(c, loc_at + N * px * sizeof(uint16_t))) || (rc = v.ps_stage.reserve(c, stage_bytes > 0 ? stage_bytes : 16)))
+        return rc;
+    if (!v.h_ps_totals) HIPCHK(c, v.h_ps_totals.try_alloc((size_t)kMaxLists));
+    unsigned char* const ix = v.ps_index.get();
+    unsigned char* const sg = v.ps_stage.get();
+    PackTotals* const d_totals = reinterpret_cast<PackTotals*>(ix + totals_at);
+    PackedStream table[kPackSetMax];
+    int Smax = 1;
+    for (int j = 0; j < n; ++j) {
+        PackedStream& t = table[j];
+        t.off = PackOffsets{sg + at[j].cnt_at,
+                            reinterpret_cast<uint32_t*>(ix + bstat_at) + (size_t)j * nb,
+                            reinterpret_cast<unsigned long long*>(ix + boff_at) + (size_t)j * nb,
+                            d_totals + j, (uint32_t)px, (uint32_t)nb,
+                            reinterpret_cast<uint16_t*>(ix + loc_at) + (size_t)j * px};
+        t.dep = reinterpret_cast<const float2*>(sg + at[j].dep_at);
+        t.col = sg + at[j].col_at;
+        t.E = h[j].E;
+        t.S = h[j].S;
+        t.half = h[j].format == kPackHalf ? 1u : 0u;
+        Smax = (int)h[j].S > Smax ? (int)h[j].S : Smax;
+        // each stream is uploaded once, as it is: its counts and depths lie together in it as they do in the staging
+        const unsigned char* in = static_cast<const unsigned char*>(streams[j]);
+        HIPCHK(c, hipMemcpyAsync(sg + at[j].cnt_at, in + kPackHeaderBytes, lay[j].colour_off - kPackHeaderBytes,
+                                 hipMemcpyHostToDevice, v.stream));
+        if (lay[j].colour_bytes)
+            HIPCHK(c, hipMemcpyAsync(sg + at[j].col_at, in + lay[j].colour_off, lay[j].colour_bytes, hipMemcpyHostToDevice, v.stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(ix, table, N * sizeof(PackedStream), hipMemcpyHostToDevice, v.stream));
+    // every stream's counts are validated before a kernel reads an entry that they place
+    const PackedStream* const d_table = reinterpret_cast<const PackedStream*>(ix);
+    float ms = 0.0f;
+    const auto offsets = [&]() -> Launched {
+        return {launch_pack_offsets_set(d_table, n, (uint32_t)px, (uint32_t)nb, v.stream), "pack_count_set_kernel"};
+    };
+    if ((rc = view_timed(c, who, &ms, offsets, {{v.h_ps_totals.get(), d_totals, N * sizeof(PackTotals)}}))) return rc;
+    for (int j = 0; j < n; ++j)
+        if (v.h_ps_totals[j].bad) return fail(c, -1, pack_rejected(who, j) + pack_bad_counts(v.h_ps_totals[j], h[j]));
+    return view_merge(c, PackedSource{d_table, n, (int)h[0].W}, Smax, h[0].pv_g, who, ms);
 }
 
 int insitu_view_render(insitu_ctx* c, const insitu_camera* cam, int out_w, int out_h, void* host_out, size_t cap) {

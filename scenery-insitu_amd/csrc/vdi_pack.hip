@@ -11,6 +11,8 @@
 //     takes entries l, l + 64, ... of the run and finds each one's pixel by a binary search over the wave's 64
 //     prefix values (256 B of LDS) -- so every section access of a wave is one contiguous piece (1 KiB of
 //     float colour) and the accesses to one list are contiguous too.
+//   pack_count_set_kernel / pack_scan_set_kernel: the two offset passes over every stream of a set of packed
+//     streams in one launch each (insitu_view_bind_packed_set).
 // No atomics anywhere: the order of the bytes is a function of the counts alone.
 // The compact view layout (ViewVdi with loc) holds its entries in the sections' order already:
 // pack_count_kernel also leaves every pixel's offset inside its block (loc), the FLOAT stream is copied to and from
@@ -46,9 +48,8 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t m) {
     return m;
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(256) void pack_count_kernel(const PackOffsets P) {
+// the two offset passes, over one VDI's counts (pack_count_kernel, pack_scan_kernel) or a stream of a set's
+__device__ __forceinline__ void pack_count_block(const PackOffsets& P) {
     __shared__ uint32_t s_sum[4], s_max[4];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const uint32_t p = blockIdx.x * (uint32_t)kPackBlockPx + threadIdx.x;
@@ -71,8 +72,7 @@ __global__ __launch_bounds__(256) void pack_count_kernel(const PackOffsets P) {
 }
 
 // One wave.  Four steps' block sums are loaded together (their latencies overlap); each step is a 64-wide scan.
-__global__ __launch_bounds__(64) void pack_scan_kernel(const PackOffsets P, uint32_t S, int check_E,
-                                                       unsigned long long expect_E) {
+__device__ __forceinline__ void pack_scan_wave(const PackOffsets& P, uint32_t S, int check_E, unsigned long long expect_E) {
     const int lane = threadIdx.x;
     unsigned long long carry = 0;
     uint32_t mx = 0;
@@ -98,6 +98,27 @@ __global__ __launch_bounds__(64) void pack_scan_kernel(const PackOffsets P, uint
         P.totals->max_count = mx;
         P.totals->bad = (mx > S || (check_E && carry != expect_E)) ? 1u : 0u;
     }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void pack_count_kernel(const PackOffsets P) { pack_count_block(P); }
+
+__global__ __launch_bounds__(64) void pack_scan_kernel(const PackOffsets P, uint32_t S, int check_E,
+                                                       unsigned long long expect_E) {
+    pack_scan_wave(P, S, check_E, expect_E);
+}
+
+// The same over every stream of a set in one launch each: blockIdx.y, and the scan's one wave per block, pick the
+// stream; its S and E are the header's, and the counts must add up to E (insitu_view_bind_packed_set).
+__global__ __launch_bounds__(256) void pack_count_set_kernel(const PackedStream* set) {
+    const PackOffsets P = set[blockIdx.y].off;
+    pack_count_block(P);
+}
+
+__global__ __launch_bounds__(64) void pack_scan_set_kernel(const PackedStream* set) {
+    const PackedStream s = set[blockIdx.x];
+    pack_scan_wave(s.off, s.S, 1, s.E);
 }
 
 namespace {
@@ -212,6 +233,16 @@ hipError_t launch_pack_offsets(const PackOffsets& o, int S, int check_E, unsigne
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(pack_scan_kernel, dim3(1), dim3(64), 0, s, o, (uint32_t)S, check_E, expect_E);
+    return hipGetLastError();
+}
+
+hipError_t launch_pack_offsets_set(const PackedStream* set, int n, uint32_t px, uint32_t nblocks, hipStream_t s) {
+    if (!set || n < 1 || n > kMaxLists || px == 0 || nblocks != (px + (uint32_t)kPackBlockPx - 1u) / (uint32_t)kPackBlockPx)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pack_count_set_kernel, dim3(nblocks, (unsigned)n), dim3(256), 0, s, set);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(pack_scan_set_kernel, dim3((unsigned)n), dim3(64), 0, s, set);
     return hipGetLastError();
 }
 

@@ -99,6 +99,54 @@ inline const char* pack_parse(const void* data, size_t bytes, PackHeader* h, Pac
     return nullptr;
 }
 
+// ---- a set of streams, bound as one merged VDI (insitu_view_bind_packed_set) ----
+constexpr int kPackSetMax = 32;   // (kMaxLists)
+
+// The headers and layouts of n streams that are to be merged: null when n is 1..kPackSetMax, every stream passes
+// pack_parse, and all of them have stream 0's W, H and pv_g (the 64 bytes compared as they are); else what is wrong,
+// with *index the stream it is wrong with (-1: the set itself).  S and the format may differ from stream to stream.
+// headers and layouts have room for kPackSetMax entries; those before *index are filled in.
+inline const char* pack_set_parse(const void* const* streams, const size_t* bytes, int n, PackHeader* headers,
+                                  PackLayout* layouts, int* index) {
+    *index = -1;
+    if (!streams || !bytes) return "null argument";
+    if (n < 1 || n > kPackSetMax) return "needs 1 to 32 streams";
+    for (int j = 0; j < n; ++j) {
+        *index = j;
+        if (const char* why = pack_parse(streams[j], bytes[j], &headers[j], &layouts[j])) return why;
+        if (headers[j].W != headers[0].W || headers[j].H != headers[0].H) return "W and H differ from stream 0's";
+        if (memcmp(headers[j].pv_g, headers[0].pv_g, sizeof headers[j].pv_g) != 0)
+            return "the generating camera differs from stream 0's";
+    }
+    *index = -1;
+    return nullptr;
+}
+
+// Where the streams of a parsed set lie in their one staging allocation: per stream the counts, the depth section
+// and the colour section, each at a multiple of 16 bytes, stream after stream.
+struct PackSetStage {
+    size_t cnt_at, dep_at, col_at;
+};
+
+// false when the staging does not fit a size_t.  (A parsed layout's sections are below 2^43 bytes each, so the sum
+// over kPackSetMax streams stays below 2^50: no 64-bit sum wraps.)
+inline bool pack_set_stage(const PackLayout* layouts, int n, PackSetStage* at, size_t* total) {
+    if (n < 1 || n > kPackSetMax) return false;
+    const auto pad16 = [](uint64_t v) { return (v + 15u) & ~(uint64_t)15u; };
+    uint64_t off = 0;
+    for (int j = 0; j < n; ++j) {
+        const uint64_t cnt = pad16(layouts[j].px), dep = pad16((uint64_t)layouts[j].depth_bytes);
+        const uint64_t col = pad16((uint64_t)layouts[j].colour_bytes);
+        if (off + cnt + dep + col > (uint64_t)SIZE_MAX) return false;
+        at[j].cnt_at = (size_t)off;
+        at[j].dep_at = (size_t)(off + cnt);
+        at[j].col_at = (size_t)(off + cnt + dep);
+        off += cnt + dep + col;
+    }
+    *total = (size_t)off;
+    return true;
+}
+
 // binary32 -> binary16, round to nearest even, by integer operations (numpy's astype(float16), bit for bit:
 // subnormal halves are produced, anything that rounds beyond 65504 is infinity, a NaN keeps its top payload bits
 // and stays a NaN).  Independent of the kernel's rounding and denormal modes.  gfx950's own conversion gives the

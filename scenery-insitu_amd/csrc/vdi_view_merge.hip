@@ -12,6 +12,9 @@
 // For the compact view layout the count kernel also stores every pixel's merged length as its
 // count, the offset passes of vdi_pack.hip run between the two kernels, and the merge writes each list where
 // view_list_at puts it.
+// Both kernels take their lists from a ViewSource or, the same loop instantiated again, from a PackedSource: the
+// staged streams of insitu_view_bind_packed_set, read in place through each stream's own
+// offsets; vdi_view_source.h holds what differs between the two.
 #include "insitu_device.h"
 #include "insitu_kernels.h"
 #include "vdi_view_source.h"
@@ -33,7 +36,9 @@ __device__ __forceinline__ int wave_max(int m) {
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void view_merge_count_kernel(const ViewSource P, const int W, const int H, const int S,
+// SRC: ViewSource, or PackedSource (the lists of a set of packed streams); vdi_view_source.h has what differs.
+template <class SRC>
+__global__ __launch_bounds__(256) void view_merge_count_kernel(const SRC P, const int W, const int H, const int S,
                                                                MergeTotals* tot, uint8_t* cnt) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int tiles_x = (W + 7) >> 3, tiles_y = (H + 7) >> 3;
@@ -43,14 +48,14 @@ __global__ __launch_bounds__(256) void view_merge_count_kernel(const ViewSource 
     const int x = tx * 8 + (lane & 7), y = ty * 8 + (lane >> 3);
     int m = 0;
     if (x < W && y < H) {
-        const ViewAt at = view_at(P, x, y, H, S);
+        const auto at = src_at(P, x, y, W, H, S);
         int taken = 0;   // the entries the merge takes: a list also ends at a start the merge never picks (not < 100000)
         for (int j = 0; j < P.n; ++j) {
-            const int slots = view_slots(P, j, x, y, S);
-            const size_t e0 = at.e0 + (size_t)j * at.lstride;
+            const int slots = src_slots(P, at, j, x, y, S);
+            const auto run = src_list(P, at, j);
             int c = 0, t = -1;
             for (; c < slots; ++c) {
-                const float start = P.dep[e0 + (size_t)c * at.estride].x;
+                const float start = run_dep(run, run.e0 + (size_t)c * run.estride).x;
                 if (start == 0.0f) break;
                 if (t < 0 && !(start < 100000.0f)) t = c;
             }
@@ -69,8 +74,8 @@ __global__ __launch_bounds__(256) void view_merge_count_kernel(const ViewSource 
 // registers (every access unrolled over the lists); beyond that the compiler spills them (VMAX = 32: 2052 bytes
 // of scratch per lane), so they live in LDS, one column per lane ([list][lane of the block]: no bank conflicts on
 // the scan, no barrier -- a lane touches its own column only), and the scan runs over the n lists there are.
-template <int VMAX>
-__global__ __launch_bounds__(256) void view_merge_kernel(const ViewSource P, const int S, const ViewVdi V, MergeTotals* tot) {
+template <int VMAX, class SRC>
+__global__ __launch_bounds__(256) void view_merge_kernel(const SRC P, const int S, const ViewVdi V, MergeTotals* tot) {
     constexpr bool kLds = VMAX > 8;
     __shared__ float lfs[kLds ? VMAX * 256 : 1];
     __shared__ uint32_t lst[kLds ? VMAX * 256 : 1];
@@ -83,13 +88,13 @@ __global__ __launch_bounds__(256) void view_merge_kernel(const ViewSource P, con
     int m = 0;
     uint32_t overlaps = 0;
     if (x < V.W && y < H) {
-        const ViewAt at = view_at(P, x, y, H, S);
+        const auto at = src_at(P, x, y, V.W, H, S);
         float fs[kLds ? 1 : VMAX];
         uint32_t st[kLds ? 1 : VMAX];
         auto front_of = [&](int j, float& f, uint32_t& left) {
-            const int slots = view_slots(P, j, x, y, S);
+            const int slots = src_slots(P, at, j, x, y, S);
             left = (uint32_t)slots;
-            f = slots > 0 ? P.dep[at.e0 + (size_t)j * at.lstride].x : 0.0f;
+            f = slots > 0 ? src_front(P, at, j) : 0.0f;
         };
         if constexpr (kLds) {
             for (int j = 0; j < n; ++j) front_of(j, lfs[j * 256 + tid], lst[j * 256 + tid]);
@@ -130,11 +135,12 @@ __global__ __launch_bounds__(256) void view_merge_kernel(const ViewSource P, con
                     if (j == idx) s = st[j];
             }
             const uint32_t left = s & 0xffffu, taken = s >> 16;
-            const size_t e = at.e0 + (size_t)idx * at.lstride + (size_t)taken * at.estride;
-            const float2 se = P.dep[e];
-            const float4 colour = P.col[e];
+            const auto run = src_list(P, at, idx);
+            const size_t e = run.e0 + (size_t)taken * run.estride;
+            const float2 se = run_dep(run, e);
+            const float4 colour = run_col(run, e);
             // advance that list
-            const float nxt = left > 1u ? P.dep[e + at.estride].x : 0.0f;
+            const float nxt = left > 1u ? run_dep(run, e + run.estride).x : 0.0f;
             const uint32_t ns = (left - 1u) | ((taken + 1u) << 16);
             if constexpr (kLds) {
                 lfs[idx * 256 + tid] = nxt;
@@ -171,28 +177,47 @@ unsigned merge_blocks(int W, int H) {
     return (unsigned)((tiles + 3) / 4);
 }
 
-}  // namespace
-
-hipError_t launch_view_merge_count(const ViewSource& src, int W, int H, int S, MergeTotals* tot, uint8_t* cnt,
-                                   hipStream_t s) {
+template <class SRC>
+hipError_t merge_count_launch(const SRC& src, int W, int H, int S, MergeTotals* tot, uint8_t* cnt, hipStream_t s) {
     const unsigned blocks = merge_blocks(W, H);
     if (!blocks || S <= 0 || src.n < 1 || src.n > kMaxLists) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(tot, 0, sizeof(MergeTotals), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(view_merge_count_kernel, dim3(blocks), dim3(256), 0, s, src, W, H, S, tot, cnt);
+    hipLaunchKernelGGL(view_merge_count_kernel<SRC>, dim3(blocks), dim3(256), 0, s, src, W, H, S, tot, cnt);
     return hipGetLastError();
 }
 
-hipError_t launch_view_merge(const ViewSource& src, int S, const ViewVdi& dst, MergeTotals* tot, hipStream_t s) {
+template <class SRC>
+hipError_t merge_launch(const SRC& src, int S, const ViewVdi& dst, MergeTotals* tot, hipStream_t s) {
     const unsigned blocks = merge_blocks(dst.W, dst.H);
     if (!blocks || S <= 0 || dst.S <= 0 || dst.S > 255 || src.n < 1 || src.n > kMaxLists || (dst.loc && !dst.boff))
         return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(&tot->overlaps, 0, sizeof tot->overlaps, s);
     if (e != hipSuccess) return e;
-    if (src.n <= 8) hipLaunchKernelGGL(view_merge_kernel<8>, dim3(blocks), dim3(256), 0, s, src, S, dst, tot);
-    else if (src.n <= 16) hipLaunchKernelGGL(view_merge_kernel<16>, dim3(blocks), dim3(256), 0, s, src, S, dst, tot);
-    else hipLaunchKernelGGL(view_merge_kernel<kMaxLists>, dim3(blocks), dim3(256), 0, s, src, S, dst, tot);
+    if (src.n <= 8) hipLaunchKernelGGL((view_merge_kernel<8, SRC>), dim3(blocks), dim3(256), 0, s, src, S, dst, tot);
+    else if (src.n <= 16) hipLaunchKernelGGL((view_merge_kernel<16, SRC>), dim3(blocks), dim3(256), 0, s, src, S, dst, tot);
+    else hipLaunchKernelGGL((view_merge_kernel<kMaxLists, SRC>), dim3(blocks), dim3(256), 0, s, src, S, dst, tot);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_view_merge_count(const ViewSource& src, int W, int H, int S, MergeTotals* tot, uint8_t* cnt,
+                                   hipStream_t s) {
+    return merge_count_launch(src, W, H, S, tot, cnt, s);
+}
+hipError_t launch_view_merge_count(const PackedSource& src, int W, int H, int S, MergeTotals* tot, uint8_t* cnt,
+                                   hipStream_t s) {
+    if (!src.streams || src.W != W) return hipErrorInvalidValue;
+    return merge_count_launch(src, W, H, S, tot, cnt, s);
+}
+
+hipError_t launch_view_merge(const ViewSource& src, int S, const ViewVdi& dst, MergeTotals* tot, hipStream_t s) {
+    return merge_launch(src, S, dst, tot, s);
+}
+hipError_t launch_view_merge(const PackedSource& src, int S, const ViewVdi& dst, MergeTotals* tot, hipStream_t s) {
+    if (!src.streams || src.W != dst.W) return hipErrorInvalidValue;
+    return merge_launch(src, S, dst, tot, s);
 }
 
 }  // namespace insitu

@@ -45,7 +45,7 @@ EXPORTED_SYMBOLS = (
     "insitu_gather_composited_vdi_set", "insitu_local_group_create", "insitu_local_group_destroy",
     "insitu_set_option", "insitu_read_region", "insitu_frame_pipelined", "insitu_pipeline_flush",
     "insitu_view_bind", "insitu_view_bind_host", "insitu_view_bind_host_set", "insitu_view_render",
-    "insitu_view_pack_bytes", "insitu_view_pack", "insitu_view_bind_packed",
+    "insitu_view_pack_bytes", "insitu_view_pack", "insitu_view_bind_packed", "insitu_view_bind_packed_set",
 )
 
 # enum insitu_option
@@ -143,6 +143,7 @@ def load() -> ctypes.CDLL:
         "insitu_view_pack_bytes": (sz, [vp, i]),
         "insitu_view_pack": (i, [vp, i, vp, sz, ctypes.POINTER(sz)]),
         "insitu_view_bind_packed": (i, [vp, vp, sz]),
+        "insitu_view_bind_packed_set": (i, [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), i]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -320,6 +320,20 @@ class InSituContext:
             raise ValueError("view_bind_packed: expected bytes or a one-dimensional uint8 array")
         self._check(self.lib.insitu_view_bind_packed(self.h, b.ctypes.data, b.nbytes), "insitu_view_bind_packed")
 
+    def view_bind_packed_set(self, streams):
+        """Bind the per-pixel merge of several packed streams of one window and one generating camera (a sequence of
+        bytes-likes or uint8 arrays; vdi_io.merge_packed on the GPU): the whole scene of a run from its ranks'
+        view_pack outputs, merged straight from the streams.  S and the format may differ from stream to stream."""
+        bs = [np.ascontiguousarray(np.frombuffer(b, np.uint8) if isinstance(b, (bytes, bytearray, memoryview)) else b)
+              for b in streams]
+        for b in bs:
+            if b.dtype != np.uint8 or b.ndim != 1:
+                raise ValueError("view_bind_packed_set: expected bytes or one-dimensional uint8 arrays")
+        n = len(bs)
+        ptrs = (ctypes.c_void_p * max(n, 1))(*[b.ctypes.data for b in bs])
+        sizes = (ctypes.c_size_t * max(n, 1))(*[b.nbytes for b in bs])
+        self._check(self.lib.insitu_view_bind_packed_set(self.h, ptrs, sizes, n), "insitu_view_bind_packed_set")
+
     def stats(self) -> dict:
         """insitu_stats as a dictionary, one key per field of native.Stats: the last frame's times and counters, and
         of the bound VDI view_slots, view_overlaps, view_entries (its stored entries), view_bytes (device bytes of

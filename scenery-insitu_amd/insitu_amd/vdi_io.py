@@ -29,6 +29,9 @@ project's own format, what stands in for the compacted VDI the reference streams
 functions here are pure numpy on the reference layout, byte for byte what `InSituContext.view_pack` produces on the
 GPU, so a client without a GPU or this library's native half can read a stream.
 
+`merge_packed` merges a set of packed streams into one, as
+`InSituContext.view_bind_packed_set` binds them on the GPU.
+
 `merge_vdis` is the merged bind in numpy: the VDIs of one frame and camera -- the per-rank
 SubVDI dumps, say -- combined per pixel into one lossless VDI, as `InSituContext.view_bind_host_set` combines them on
 the GPU.
@@ -297,6 +300,41 @@ def unpack_vdi(buf) -> tuple[np.ndarray, np.ndarray, np.ndarray, int]:
     depth[live] = dep
     return (np.ascontiguousarray(colour.transpose(1, 0, 2, 3)),
             np.ascontiguousarray(depth.transpose(1, 0, 2, 3)).reshape(W, H, 2 * S), np.asarray(pv, np.float32), int(fmt))
+
+
+def merge_packed(streams, fmt: int = PACK_FLOAT) -> np.ndarray:
+    """Packed streams of one window and one generating camera -> the packed stream of their merged VDI, what
+    `InSituContext.view_bind_packed_set` binds on the GPU, for a client without one: each stream unpacked,
+    zero-padded to the largest S, merged by `merge_vdis` and packed in `fmt` with the common pv_g.  ValueError on
+    an empty set or more than 32 streams, on differing W, H or pv_g (compared bit for bit), and on everything
+    `unpack_vdi` or `merge_vdis` raises."""
+    streams = list(streams)
+    if not 1 <= len(streams) <= MERGE_MAX_LISTS:
+        raise ValueError(f"expected 1 to {MERGE_MAX_LISTS} streams, got {len(streams)}")
+    vdis = []
+    for j, b in enumerate(streams):
+        try:
+            vdis.append(unpack_vdi(b))
+        except ValueError as e:
+            raise ValueError(f"stream {j}: {e}") from None
+    c0, _, pv0, _ = vdis[0]
+    for j, (c, _, pv, _) in enumerate(vdis):
+        if c.shape[:2] != c0.shape[:2]:
+            raise ValueError(f"stream {j}: W and H differ from stream 0's")
+        if pv.tobytes() != pv0.tobytes():
+            raise ValueError(f"stream {j}: the generating camera differs from stream 0's")
+    s_max = max(c.shape[2] for c, _, _, _ in vdis)
+    cols, deps = [], []
+    for c, d, _, _ in vdis:
+        W, H, S = c.shape[:3]
+        cp = np.zeros((W, H, s_max, 4), np.float32)
+        dp = np.zeros((W, H, s_max, 2), np.float32)
+        cp[:, :, :S] = c
+        dp[:, :, :S] = d.reshape(W, H, S, 2)
+        cols.append(cp)
+        deps.append(dp.reshape(W, H, 2 * s_max))
+    col, dep, _ = merge_vdis(cols, deps)
+    return pack_vdi(col, dep, pv0, fmt)
 
 
 def write_packed(path: str | Path, colour: np.ndarray, depth: np.ndarray, pv_g, fmt: int = PACK_FLOAT) -> Path:

@@ -28,8 +28,17 @@ bound again in the compact view layout: the layout's device bytes (insitu_stats.
 the orbit with its passes alternating between the two layouts, with --pack the pack and bind-packed times, with
 --merged the merged bind and its orbit.  The compact figures stand beside the dense ones in the JSON.
 
+--packed-set: the whole scene from packed streams.  Config 2 in the default context; each of
+the eight sub-VDIs is bound (INSITU_VIEW_BRICK) and packed, FLOAT and HALF; the set is bound with
+insitu_view_bind_packed_set, dense and with --compact also compact, and the FLOAT pack of the result must equal the
+FLOAT pack of INSITU_VIEW_MERGED of the same frame byte for byte (the HALF set: the HALF packs).  Beside it today's
+path, insitu_view_bind_host_set of the same eight sub-VDIs read back dense: for both the bytes uploaded, the device
+bytes staged, ms_view_bind and the wall time of the call, one warm-up and the best of three.  Prints one JSON line and
+nothing else runs.
+
 usage: python tools/view_bench.py [--brick 512] [--sim-n 512] [--views 36] [--passes 3] [--count-views 2] [--pack] [--compact]
        python tools/view_bench.py --merged [--compact] [--brick 512] [--sim-n 512] [--views 36] [--passes 2]
+       python tools/view_bench.py --packed-set [--compact] [--brick 512] [--sim-n 512]
 """
 from __future__ import annotations
 
@@ -164,6 +173,94 @@ def run_merged(args):
     print(json.dumps(res))
 
 
+def run_packed_set(args):
+    """--packed-set: the eight sub-VDIs of config 2 as packed streams, bound as one merged VDI."""
+    from insitu_amd import native, scene
+    from insitu_amd.renderer import InSituContext
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n = args.brick
+    bricks = scene.grid_bricks(n * 2, 2)
+    nb = len(bricks)
+    t0 = time.perf_counter()
+    ctx = InSituContext(W_IMG, H_IMG, max_supersegments=S, bricks_per_rank=nb, keep_passes=False)
+    ctx.set_transfer(scene.transfer_function(), scene.colormap_hot(), conv_scale=1.0 / 0.5, conv_offset=0.0)
+    for bid, (origin, vw, _) in enumerate(bricks):
+        v = scene.gray_scott(n, steps=1500, seed=1000 + bid, device=dev, sim_n=min(args.sim_n, n)).contiguous()
+        ctx.set_brick(bid, v, scene.brick_model(origin, vw), dtype=native.F32)
+        del v
+    cam = scene.orbit_camera(W_IMG, H_IMG, yaw_deg=30.0, pitch_deg=20.0, voxel_world=bricks[0][1])
+    ctx.frame(cam)
+    torch.cuda.synchronize()
+    log(f"view_bench: {nb} bricks of {n}^3 and their frame in {time.perf_counter() - t0:.1f} s")
+    streams = {"float": [], "half": []}
+    for b in range(nb):
+        ctx.view_bind(native.VIEW_BRICK, b)
+        streams["float"].append(ctx.view_pack(native.PACK_FLOAT))
+        streams["half"].append(ctx.view_pack(native.PACK_HALF))
+    ctx.view_bind(native.VIEW_MERGED)
+    merged_float = ctx.view_pack(native.PACK_FLOAT)
+    merged_half = ctx.view_pack(native.PACK_HALF)
+    px16 = (W_IMG * H_IMG + 15) // 16 * 16
+
+    def timed(bind):
+        """one warm-up (it allocates), then the best of three: the bind's kernels and the call's wall time"""
+        ms, wall = [], []
+        for _ in range(4):
+            t0 = time.perf_counter()
+            bind()
+            wall.append((time.perf_counter() - t0) * 1e3)
+            ms.append(ctx.stats()["ms_view_bind"])
+        st = ctx.stats()
+        return {"ms_view_bind": min(ms[1:]), "ms_view_bind_first": ms[0], "ms_wall": min(wall[1:]), "ms_wall_first": wall[0],
+                "view_slots": int(st["view_slots"]), "view_entries": int(st["view_entries"]),
+                "view_overlaps": int(st["view_overlaps"]), "view_layout_bytes": int(st["view_bytes"])}
+
+    layouts = {"dense": 0, "compact": 1} if args.compact else {"dense": 0}
+    res = {"metric": f"insitu_view_bind_packed_set of the {nb} sub-VDIs of config 2 ({W_IMG}x{H_IMG}, S = {S}, {nb}x{n}^3 "
+                     f"volume) against insitu_view_bind_host_set of the same sub-VDIs read back dense",
+           "timing": "one warm-up, then the best of three per bind; ms_view_bind: HIP events around the bind's kernels, "
+                     "ms_wall: the call with its uploads", "packed_set": {}, "host_set": {}}
+    for lname, layout in layouts.items():
+        ctx.set_option(native.OPT_VIEW_COMPACT, layout)
+        for fname, fmt_streams in streams.items():
+            r = timed(lambda: ctx.view_bind_packed_set(fmt_streams))
+            up = sum(int(s.size) for s in fmt_streams)
+            # staged: every stream without its header, sections padded to 16 bytes (csrc/vdi_pack_format.h
+            # pack_set_stage); index: the streams' own boff, bstat and loc, their totals and the table
+            r["bytes_uploaded"] = up
+            ents = [(int(s.size) - 128 - px16) // (ENTRY_BYTES if fname == "float" else 16) for s in fmt_streams]
+            r["device_bytes_staged"] = sum(px16 + (8 * e + 15) // 16 * 16 + ((16 if fname == "float" else 8) * e + 15) // 16 * 16
+                                           for e in ents)
+            r["device_bytes_index"] = nb * (W_IMG * H_IMG * 2 + (W_IMG * H_IMG + 255) // 256 * 12 + 16 + 80)
+            got = ctx.view_pack(native.PACK_FLOAT)
+            if fname == "float":
+                assert np.array_equal(got, merged_float), "the set bind differs from INSITU_VIEW_MERGED of the same frame"
+            else:   # the HALF streams' merge, repacked as HALF, is the HALF pack of the merged bind
+                assert np.array_equal(ctx.view_pack(native.PACK_HALF), merged_half), "HALF set bind differs"
+            del got
+            res["packed_set"][f"{lname}_{fname}"] = r
+            log(f"view_bench: packed set {lname} {fname} {json.dumps(r)}")
+    del merged_half
+    # today's path: the same sub-VDIs read back dense and bound through insitu_view_bind_host_set
+    cols = [ctx.read(native.BUF_VDI_COLOR, b) for b in range(nb)]
+    deps = [ctx.read(native.BUF_VDI_DEPTH, b) for b in range(nb)]
+    for lname, layout in layouts.items():
+        ctx.set_option(native.OPT_VIEW_COMPACT, layout)
+        r = timed(lambda: ctx.view_bind_host_set(cols, deps, cam))
+        r["bytes_uploaded"] = r["device_bytes_staged"] = sum(int(c.nbytes) + int(d.nbytes) for c, d in zip(cols, deps))
+        r["device_bytes_index"] = 0
+        assert np.array_equal(ctx.view_pack(native.PACK_FLOAT), merged_float), "the host set differs from INSITU_VIEW_MERGED"
+        res["host_set"][lname] = r
+        log(f"view_bench: host set {lname} {json.dumps(r)}")
+    res["merged_packed_bytes"] = int(merged_float.size)
+    res["merged_entries"] = (int(merged_float.size) - 128 - px16) // ENTRY_BYTES
+    ctx.set_option(native.OPT_VIEW_COMPACT, 0)
+    ctx.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--brick", type=int, default=512)
@@ -180,9 +277,13 @@ def main():
                     help="every measurement also in the compact view layout (INSITU_OPT_VIEW_COMPACT), beside dense")
     ap.add_argument("--merged", action="store_true",
                     help="INSITU_VIEW_MERGED of the flatten context against INSITU_VIEW_GATHERED of the composite_vdi one")
+    ap.add_argument("--packed-set", action="store_true",
+                    help="insitu_view_bind_packed_set of the eight packed sub-VDIs against insitu_view_bind_host_set")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("view_bench: needs a GPU (timings are HIP-event times of the kernel)")
+    if args.packed_set:
+        return run_packed_set(args)
     if args.merged:
         return run_merged(args)
     from insitu_amd import native, scene
