@@ -290,7 +290,7 @@ int insitu_read_region(insitu_ctx* ctx, int which, int slot, int x0, int x1, voi
  * flatten compositor walks them (VDICompositor.comp:58-91), every entry copied bit for bit.  The bound VDI has
  * S_m = max(1, the longest merged list) slots (insitu_stats.view_slots); more than 255 is rejected with -1.
  * With one sub-VDI (one brick, merge_bricks) it is INSITU_VIEW_BRICK of slot 0; with nranks > 1 it merges the
- * rank's own bricks only.
+ * rank's own bricks only, and insitu_view_gather_merged (below) then merges the ranks' bound VDIs on rank 0.
  * A failed insitu_view_bind* call leaves no VDI bound -- whichever of them it is, and wherever it fails. */
 int insitu_view_bind(insitu_ctx* ctx, int source, int slot);
 /* The same from host memory: a VDI in the reference layout -- colour (W,H,S,4) rgba32f and depth (W,H,2S) r32f, x
@@ -344,6 +344,37 @@ int insitu_view_bind_packed(insitu_ctx* ctx, const void* data, size_t bytes);
  * Runs on the view's own stream: legal while a pipelined frame is in flight.  insitu_stats reports it through
  * view_slots, view_overlaps, view_entries, view_bytes, view_compact and ms_view_bind. */
 int insitu_view_bind_packed_set(insitu_ctx* ctx, const void* const* streams, const size_t* bytes, int n);
+/* Gather every rank's bound VDI into one merged VDI bound on rank 0 (an addition within ABI 12: no existing call or
+ * structure changes) -- the whole scene without loss and without the host: what stands in for the MPI_Gather behind
+ * DistributedVolumes.kt:903-904 and for a viewer that reads the per-rank SubVDI dumps of :848-849, with none of the
+ * compositor's re-supersegmentation.  A collective over the context's ranks with rank 0 as the root: every rank has a
+ * VDI bound (INSITU_VIEW_MERGED, say; any bind counts), and after a successful call the root has bound exactly what
+ * insitu_view_bind_packed_set binds from the ranks' insitu_view_pack(format) streams in rank order, stream j = rank
+ * j (a message about "stream j" is about rank j): merged per pixel by start depth, the lowest rank first on a tie,
+ * entries copied bit for bit (INSITU_PACK_HALF: colours rounded to binary16 by the pack and widened exactly), S_m =
+ * max(1, the longest merged list) slots, more than 255 rejected, in the layout INSITU_OPT_VIEW_COMPACT says on the
+ * root; view_slots, view_overlaps, view_entries, view_bytes, view_compact and ms_view_bind describe it.  W, H and
+ * pv_g (its 64 bytes) must agree across the ranks; S and the layout may differ.  Only fixed-size control data -- a
+ * 128-byte header per rank, the verdict, the totals -- is read on the host: counts, depths and colours go from
+ * device to device.
+ * A peer's bound VDI is the same after the call as before it, whether the call succeeds or fails; only the root's
+ * binding changes, and on any failure the root has nothing bound.  A rank that cannot take part (nothing bound, bad
+ * `format`, a frame in flight, an allocation failure) still takes its turn, so that no rank is left waiting: the
+ * root rejects the gather, every rank returns -1, and insitu_last_error names the rank and the reason on every rank.
+ * The communicator is then ready for the next collective.  A failure of the counts' check on the device is the root's
+ * alone: a peer has returned 0 once its sections were sent.
+ * *wire_bytes (may be NULL): on the root the section bytes received from the peers, on a peer the section bytes it
+ * sent, W*H + 8*E + (16 or 8)*E; 0 with one rank.  nranks = 1: insitu_view_bind_packed of the rank's own
+ * insitu_view_pack(format) stream, whose entries take no host round trip either.  More than 32 ranks: -1 on every
+ * rank, without communicating.
+ * With nranks > 1 the call uses the context's communicator (on the view's stream), so -- unlike the other view calls
+ * -- it is NOT legal while a pipelined frame is in flight: insitu_pipeline_flush first (a rank that has one refuses).
+ * In a local group the calls are sequential, as insitu_gather's are, the peers first and the root last: a peer's call
+ * packs, leaves its offer (header, section pointers, an event) and returns 0, also when it refuses; the root's call
+ * validates the offers, pulls the sections device to device and binds, so a rejection is seen by the root alone.  A
+ * root that calls before some peer has offered returns -1 and names that rank.  An offer holds the peer's staged
+ * sections: a bind or a pack on the peer before the root's call withdraws it, and the root's call then fails. */
+int insitu_view_gather_merged(insitu_ctx* ctx, int format, unsigned long long* wire_bytes);
 int insitu_get_stats(insitu_ctx* ctx, insitu_stats* out);
 /* Set a tuning option (enum insitu_option) for the following renders; -1 on an unknown option or
  * a value out of range.  Environment variables INSITU_<OPTION NAME> (INSITU_EXACT_SEARCH,

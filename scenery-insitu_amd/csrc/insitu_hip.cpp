@@ -44,13 +44,6 @@ CompletedFrame completed_frame(const insitu_ctx* c) { return {*c->cur, c->pipe_i
 
 namespace {
 
-#define NCCLCHK(ctx, expr)                                                                         \
-    do {                                                                                           \
-        ncclResult_t r_ = (expr);                                                                  \
-        if (r_ != ncclSuccess)                                                                     \
-            return fail(ctx, -4, std::string(#expr " failed: ") + ncclGetErrorString(r_));         \
-    } while (0)
-
 // Everything of a context that is not memory: its streams' work first, then the events, the streams, the
 // communicator and the local-group slot.  The memory (every DevBuf of the context, its slots, view and bricks) is
 // freed after it, when the caller deletes the context with the device still current.
@@ -69,7 +62,7 @@ void release(insitu_ctx* c) {
             if (e) (void)hipEventDestroy(e);
         if (f.search_stream) (void)hipStreamDestroy(f.search_stream);
     }
-    for (hipEvent_t e : {c->view.ev0, c->view.ev1, c->ev_ingest, c->ev_ingest0, c->ev_gate})
+    for (hipEvent_t e : {c->view.ev0, c->view.ev1, c->view.offer.ev, c->ev_ingest, c->ev_ingest0, c->ev_gate})
         if (e) (void)hipEventDestroy(e);
     for (hipStream_t st : {c->view.stream, c->pipe_sample, c->pipe_comp})
         if (st) (void)hipStreamDestroy(st);

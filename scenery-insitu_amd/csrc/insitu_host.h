@@ -247,6 +247,20 @@ struct ViewState {
     DevBuf<unsigned char> ps_stage;     // every stream's counts, depth section and colour section, as they arrive
     DevBuf<unsigned char> ps_index;     // the PackedStream table, the streams' totals, and each stream's own boff, bstat, loc
     PinnedBuf<PackTotals> h_ps_totals;  // kMaxLists: the totals of all streams, read back in one copy
+    // the gather of the ranks' bound VDIs on rank 0 (insitu_view_gather_merged)
+    DevBuf<unsigned char> gm_ctl;       // headers (the root: one per rank) and the verdict record, as they travel
+    PinnedBuf<unsigned char> h_gm_ctl;  // the same on the host: the only bytes of a gather the host reads
+    // (local group) what a peer's call leaves for the root's: its header and where its sections lie on its device,
+    // ready once `ev` (the view's stream, behind its pack) has completed.  The sections are the peer's own buffers:
+    // a bind or a pack of the peer's before the root has pulled them withdraws the offer.
+    struct GatherOffer {
+        enum { None, Made, Withdrawn } state = None;
+        unsigned char header[128] = {};
+        const uint8_t* cnt = nullptr;
+        const float2* dep = nullptr;
+        const void* col = nullptr;
+        hipEvent_t ev = nullptr;
+    } offer;
 };
 
 struct insitu_ctx {
@@ -358,6 +372,13 @@ struct insitu_ctx {
         hipError_t e_ = (expr);                                                                    \
         if (e_ != hipSuccess)                                                                      \
             return fail(ctx, -3, std::string(#expr " failed: ") + hipGetErrorString(e_));          \
+    } while (0)
+
+#define NCCLCHK(ctx, expr)                                                                         \
+    do {                                                                                           \
+        ncclResult_t r_ = (expr);                                                                  \
+        if (r_ != ncclSuccess)                                                                     \
+            return fail(ctx, -4, std::string(#expr " failed: ") + ncclGetErrorString(r_));         \
     } while (0)
 
 bool is_root(const insitu_ctx* c);

@@ -17,8 +17,16 @@ namespace {
 
 const char* const kBadDimensions = "view bind: needs W, H > 0, at most 2^30 pixels and S in [1,255]";
 
+// a bind or a pack reuses the buffers that a local group's peer has offered to its root (insitu_view_gather_merged)
+void offer_withdraw(ViewState& v) {
+    if (v.offer.state == ViewState::GatherOffer::Made) v.offer.state = ViewState::GatherOffer::Withdrawn;
+}
+
 // every bind's first step: whatever fails after it, no VDI is bound
-void view_unbind(ViewState& v) { v.bound = v.counted = false; }
+void view_unbind(ViewState& v) {
+    v.bound = v.counted = false;
+    offer_withdraw(v);
+}
 
 // ... and its last: the generating camera, the kernels' time (the packed bind's is ms_pack as well), the overlaps a
 // merge found, and E with the block offsets where the bind ran the offset passes (else counted on demand)
@@ -391,6 +399,7 @@ int insitu_view_pack(insitu_ctx* c, int format, void* host_out, size_t cap, size
         return fail(c, -1, "insitu_view_pack: output buffer too small (" + std::to_string(lay.total) + " bytes needed)");
     const bool half = format == INSITU_PACK_HALF;
     PackSections s{};
+    offer_withdraw(v);
     if (int rc = pack_sections(c, half, lay, &s)) return rc;
     unsigned char* out = static_cast<unsigned char*>(host_out);
     // (E == 0: the sections are empty, and nothing is copied from arrays that may not exist)
@@ -416,18 +425,24 @@ std::string pack_bad_counts(const PackTotals& tot, const PackHeader& h) {
     return "the counts add up to " + std::to_string(tot.E) + ", the header says " + std::to_string(h.E);
 }
 
-// one packed stream into the view layout (insitu_view_bind_packed; a set of one); index: see pack_rejected
-int view_bind_packed_one(insitu_ctx* c, const char* who, int index, const void* data, size_t bytes) {
+// the counts and the two sections of a parsed stream where they lie: behind its header in host memory, or staged on
+// the device (insitu_view_gather_merged)
+struct PackedBytes {
+    const void* cnt;
+    const void* dep;
+    const void* col;
+    hipMemcpyKind kind;
+};
+
+// one parsed stream into the view layout; index: see pack_rejected
+int view_bind_packed_parsed(insitu_ctx* c, const char* who, int index, const PackHeader& h, const PackLayout& lay,
+                            const PackedBytes& in) {
     ViewState& v = c->view;
-    PackHeader h{};
-    PackLayout lay{};
-    if (const char* why = pack_parse(data, bytes, &h, &lay)) return fail(c, -1, pack_rejected(who, index) + why);
     HIPCHK(c, hipSetDevice(c->cfg.device));
     if (int rc = view_reserve_index(c, (int)h.W, (int)h.H)) return rc;
-    const unsigned char* in = static_cast<const unsigned char*>(data);
     // the counts go straight into the view layout, and are validated on the device before anything depends on
     // them: every count <= S, and the counts add up to E
-    HIPCHK(c, hipMemcpyAsync(v.vdi.cnt, in + kPackHeaderBytes, (size_t)lay.px, hipMemcpyHostToDevice, v.stream));
+    HIPCHK(c, hipMemcpyAsync(v.vdi.cnt, in.cnt, (size_t)lay.px, in.kind, v.stream));
     PackTotals tot{};
     float ms = 0.0f;
     if (int rc = view_count(c, who, (int)h.S, 1, h.E, &tot, &ms, no_launch)) return rc;
@@ -437,12 +452,91 @@ int view_bind_packed_one(insitu_ctx* c, const char* who, int index, const void* 
     if (int rc = view_reserve_entries(c, (int)h.S, h.E)) return rc;
     if (int rc = pack_sections(c, half, lay, &s)) return rc;
     if (h.E > 0) {
-        HIPCHK(c, hipMemcpyAsync(s.dep, in + lay.depth_off, lay.depth_bytes, hipMemcpyHostToDevice, v.stream));
-        HIPCHK(c, hipMemcpyAsync(s.col, in + lay.colour_off, lay.colour_bytes, hipMemcpyHostToDevice, v.stream));
+        HIPCHK(c, hipMemcpyAsync(s.dep, in.dep, lay.depth_bytes, in.kind, v.stream));
+        HIPCHK(c, hipMemcpyAsync(s.col, in.col, lay.colour_bytes, in.kind, v.stream));
     }
     if (int rc = view_timed(c, who, &ms, [&] { return pack_launch(v, s, half, h.E, false); })) return rc;
     view_commit(v, h.pv_g, ms, &tot, 0, true);
     return 0;
+}
+
+// one packed stream into the view layout (insitu_view_bind_packed; a set of one)
+int view_bind_packed_one(insitu_ctx* c, const char* who, int index, const void* data, size_t bytes) {
+    PackHeader h{};
+    PackLayout lay{};
+    if (const char* why = pack_parse(data, bytes, &h, &lay)) return fail(c, -1, pack_rejected(who, index) + why);
+    const unsigned char* in = static_cast<const unsigned char*>(data);
+    return view_bind_packed_parsed(c, who, index, h, lay,
+                                   {in + kPackHeaderBytes, in + lay.depth_off, in + lay.colour_off, hipMemcpyHostToDevice});
+}
+
+// The index of a set's streams, apart from the bound VDI's (ViewState::ps_index): table | totals | per stream boff |
+// bstat | loc
+struct PackSetIndex {
+    size_t px, nb, totals_at, boff_at, bstat_at, loc_at, bytes;
+};
+PackSetIndex pack_set_index(int n, uint64_t pixels) {
+    PackSetIndex x{};
+    const size_t N = (size_t)n;
+    x.px = (size_t)pixels;
+    x.nb = (size_t)view_blocks(pixels);
+    x.totals_at = (N * sizeof(PackedStream) + 15) & ~(size_t)15;
+    x.boff_at = x.totals_at + N * sizeof(PackTotals);
+    x.bstat_at = x.boff_at + N * x.nb * sizeof(unsigned long long);
+    x.loc_at = (x.bstat_at + N * x.nb * sizeof(uint32_t) + 15) & ~(size_t)15;
+    x.bytes = x.loc_at + N * x.px * sizeof(uint16_t);
+    return x;
+}
+
+// room for the n parsed streams of a set and their index: at[j] says where stream j is staged in ps_stage
+int view_set_reserve(insitu_ctx* c, const char* who, const PackLayout* lay, int n, PackSetStage* at) {
+    ViewState& v = c->view;
+    size_t stage_bytes = 0;
+    if (!pack_set_stage(lay, n, at, &stage_bytes)) return fail(c, -1, std::string(who) + ": the streams' size does not fit");
+    int rc = 0;
+    if ((rc = v.ps_index.reserve(c, pack_set_index(n, lay[0].px).bytes)) ||
+        (rc = v.ps_stage.reserve(c, stage_bytes > 0 ? stage_bytes : 16)))
+        return rc;
+    if (!v.h_ps_totals) HIPCHK(c, v.h_ps_totals.try_alloc((size_t)kMaxLists));
+    return 0;
+}
+
+// The bind of n >= 2 staged streams (view_set_reserve; their counts and sections are in ps_stage, or on their way
+// there on the view's stream): the PackedStream table, the offset passes over every stream's counts -- which
+// validate them before a kernel reads an entry that they place -- and the merge.
+int view_set_bind(insitu_ctx* c, const char* who, const PackHeader* h, const PackLayout* lay, const PackSetStage* at, int n) {
+    ViewState& v = c->view;
+    if (int rc = view_reserve_index(c, (int)h[0].W, (int)h[0].H)) return rc;
+    const PackSetIndex x = pack_set_index(n, lay[0].px);
+    unsigned char* const ix = v.ps_index.get();
+    unsigned char* const sg = v.ps_stage.get();
+    PackTotals* const d_totals = reinterpret_cast<PackTotals*>(ix + x.totals_at);
+    PackedStream table[kPackSetMax];
+    int Smax = 1;
+    for (int j = 0; j < n; ++j) {
+        PackedStream& t = table[j];
+        t.off = PackOffsets{sg + at[j].cnt_at,
+                            reinterpret_cast<uint32_t*>(ix + x.bstat_at) + (size_t)j * x.nb,
+                            reinterpret_cast<unsigned long long*>(ix + x.boff_at) + (size_t)j * x.nb,
+                            d_totals + j, (uint32_t)x.px, (uint32_t)x.nb,
+                            reinterpret_cast<uint16_t*>(ix + x.loc_at) + (size_t)j * x.px};
+        t.dep = reinterpret_cast<const float2*>(sg + at[j].dep_at);
+        t.col = sg + at[j].col_at;
+        t.E = h[j].E;
+        t.S = h[j].S;
+        t.half = h[j].format == kPackHalf ? 1u : 0u;
+        Smax = (int)h[j].S > Smax ? (int)h[j].S : Smax;
+    }
+    HIPCHK(c, hipMemcpyAsync(ix, table, (size_t)n * sizeof(PackedStream), hipMemcpyHostToDevice, v.stream));
+    const PackedStream* const d_table = reinterpret_cast<const PackedStream*>(ix);
+    float ms = 0.0f;
+    const auto offsets = [&]() -> Launched {
+        return {launch_pack_offsets_set(d_table, n, (uint32_t)x.px, (uint32_t)x.nb, v.stream), "pack_count_set_kernel"};
+    };
+    if (int rc = view_timed(c, who, &ms, offsets, {{v.h_ps_totals.get(), d_totals, (size_t)n * sizeof(PackTotals)}})) return rc;
+    for (int j = 0; j < n; ++j)
+        if (v.h_ps_totals[j].bad) return fail(c, -1, pack_rejected(who, j) + pack_bad_counts(v.h_ps_totals[j], h[j]));
+    return view_merge(c, PackedSource{d_table, n, (int)h[0].W}, Smax, h[0].pv_g, who, ms);
 }
 
 }  // namespace
@@ -472,38 +566,11 @@ int insitu_view_bind_packed_set(insitu_ctx* c, const void* const* streams, const
     int index = -1;
     if (const char* why = pack_set_parse(streams, bytes, n, h, lay, &index))
         return fail(c, -1, index < 0 ? std::string(who) + ": " + why : pack_rejected(who, index) + why);
-    size_t stage_bytes = 0;
-    if (!pack_set_stage(lay, n, at, &stage_bytes)) return fail(c, -1, std::string(who) + ": the streams' size does not fit");
     HIPCHK(c, hipSetDevice(c->cfg.device));
-    if (int rc = view_reserve_index(c, (int)h[0].W, (int)h[0].H)) return rc;
-    // the index of the streams, apart from the bound VDI's: table | totals | per stream boff | bstat | loc
-    const size_t px = (size_t)lay[0].px, nb = (size_t)view_blocks((uint64_t)px), N = (size_t)n;
-    const size_t totals_at = (N * sizeof(PackedStream) + 15) & ~(size_t)15;
-    const size_t boff_at = totals_at + N * sizeof(PackTotals);
-    const size_t bstat_at = boff_at + N * nb * sizeof(unsigned long long);
-    const size_t loc_at = (bstat_at + N * nb * sizeof(uint32_t) + 15) & ~(size_t)15;
-    int rc = 0;
-    if ((rc = v.ps_index.reserve(c, loc_at + N * px * sizeof(uint16_t))) || (rc = v.ps_stage.reserve(c, stage_bytes > 0 ? stage_bytes : 16)))
-        return rc;
-    if (!v.h_ps_totals) HIPCHK(c, v.h_ps_totals.try_alloc((size_t)kMaxLists));
-    unsigned char* const ix = v.ps_index.get();
+    if (int rc = view_stream(c)) return rc;
+    if (int rc = view_set_reserve(c, who, lay, n, at)) return rc;
     unsigned char* const sg = v.ps_stage.get();
-    PackTotals* const d_totals = reinterpret_cast<PackTotals*>(ix + totals_at);
-    PackedStream table[kPackSetMax];
-    int Smax = 1;
     for (int j = 0; j < n; ++j) {
-        PackedStream& t = table[j];
-        t.off = PackOffsets{sg + at[j].cnt_at,
-                            reinterpret_cast<uint32_t*>(ix + bstat_at) + (size_t)j * nb,
-                            reinterpret_cast<unsigned long long*>(ix + boff_at) + (size_t)j * nb,
-                            d_totals + j, (uint32_t)px, (uint32_t)nb,
-                            reinterpret_cast<uint16_t*>(ix + loc_at) + (size_t)j * px};
-        t.dep = reinterpret_cast<const float2*>(sg + at[j].dep_at);
-        t.col = sg + at[j].col_at;
-        t.E = h[j].E;
-        t.S = h[j].S;
-        t.half = h[j].format == kPackHalf ? 1u : 0u;
-        Smax = (int)h[j].S > Smax ? (int)h[j].S : Smax;
         // each stream is uploaded once, as it is: its counts and depths lie together in it as they do in the staging
         const unsigned char* in = static_cast<const unsigned char*>(streams[j]);
         HIPCHK(c, hipMemcpyAsync(sg + at[j].cnt_at, in + kPackHeaderBytes, lay[j].colour_off - kPackHeaderBytes,
@@ -511,17 +578,235 @@ int insitu_view_bind_packed_set(insitu_ctx* c, const void* const* streams, const
         if (lay[j].colour_bytes)
             HIPCHK(c, hipMemcpyAsync(sg + at[j].col_at, in + lay[j].colour_off, lay[j].colour_bytes, hipMemcpyHostToDevice, v.stream));
     }
-    HIPCHK(c, hipMemcpyAsync(ix, table, N * sizeof(PackedStream), hipMemcpyHostToDevice, v.stream));
-    // every stream's counts are validated before a kernel reads an entry that they place
-    const PackedStream* const d_table = reinterpret_cast<const PackedStream*>(ix);
+    return view_set_bind(c, who, h, lay, at, n);
+}
+
+// ---- the ranks' bound VDIs gathered into one merged VDI on rank 0 ----
+namespace {
+
+// a rank's part in a gather: its stream's header and layout, and where the sections lie on its device
+struct GatherStream {
+    PackHeader h{};
+    PackLayout lay{};
+    PackSections s{};
+    uint32_t refusal = kGatherAccepted;   // else why the rank cannot take part (it still has its turn in the protocol)
+};
+
+// what travels back from the root: kGatherAccepted, or the rank the gather fails on and why
+struct GatherVerdict {
+    uint32_t reason;
+    int32_t rank;
+    uint32_t pad[2];
+};
+
+int gather_rejected(insitu_ctx* c, const char* who, int rank, uint32_t reason) {
+    return fail(c, -1, std::string(who) + ": rank " + std::to_string(rank) + " rejected: " + pack_gather_reason_text(reason));
+}
+
+// insitu_view_pack up to the sections: the bound VDI's stream on the device, nothing of it copied out
+int gather_prepare(insitu_ctx* c, int format, const char* who, GatherStream* g) {
+    ViewState& v = c->view;
+    if (!v.bound) g->refusal = kGatherNothingBound;
+    else if (!pack_format_ok(format)) g->refusal = kGatherBadFormatArgument;
+    else if (c->N > 1 && c->pipe_inflight) g->refusal = kGatherFrameInFlight;
+    if (g->refusal) return 0;
     float ms = 0.0f;
-    const auto offsets = [&]() -> Launched {
-        return {launch_pack_offsets_set(d_table, n, (uint32_t)px, (uint32_t)nb, v.stream), "pack_count_set_kernel"};
-    };
-    if ((rc = view_timed(c, who, &ms, offsets, {{v.h_ps_totals.get(), d_totals, N * sizeof(PackTotals)}}))) return rc;
-    for (int j = 0; j < n; ++j)
-        if (v.h_ps_totals[j].bad) return fail(c, -1, pack_rejected(who, j) + pack_bad_counts(v.h_ps_totals[j], h[j]));
-    return view_merge(c, PackedSource{d_table, n, (int)h[0].W}, Smax, h[0].pv_g, who, ms);
+    if (int rc = pack_count_bound(c, &ms, who)) return rc;
+    PackHeader& h = g->h;
+    h.format = (uint32_t)format; h.W = (uint32_t)v.vdi.W; h.H = (uint32_t)v.vdi.H; h.S = (uint32_t)v.vdi.S;
+    h.E = v.pk_E;
+    std::memcpy(h.pv_g, v.pv_g, sizeof h.pv_g);
+    if (!pack_layout(h.format, h.W, h.H, h.S, h.E, &g->lay)) return fail(c, -1, std::string(who) + ": the stream's size does not fit");
+    const bool half = format == INSITU_PACK_HALF;
+    offer_withdraw(v);
+    if (int rc = pack_sections(c, half, g->lay, &g->s)) {
+        if (rc != -5) return rc;
+        g->refusal = kGatherAllocationFailed;
+        return 0;
+    }
+    if (int rc = view_timed(c, who, &ms, [&] { return pack_launch(v, g->s, half, h.E, true); })) return rc;
+    v.ms_pack = ms;
+    return 0;
+}
+
+unsigned long long gather_section_bytes(const PackLayout& lay) {
+    return (unsigned long long)lay.px + (unsigned long long)lay.depth_bytes + (unsigned long long)lay.colour_bytes;
+}
+
+int view_gather(insitu_ctx* c, int format, unsigned long long* wire_bytes, const char* who) {
+    ViewState& v = c->view;
+    using Offer = ViewState::GatherOffer;
+    const int N = c->N;
+    const bool root = is_root(c), local = c->group != nullptr, rccl = N > 1 && !local;
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    if (int rc = view_stream(c)) return rc;
+    // the communicator is used on the view's stream: what the frame's stages left on theirs is done first
+    if (rccl && !c->pipe_inflight) HIPCHK(c, hipStreamSynchronize(c->stream));
+    GatherStream mine;
+    if (int rc = gather_prepare(c, format, who, &mine)) return rc;
+    unsigned char head[kPackHeaderBytes];
+    if (mine.refusal) pack_write_refusal(head, mine.refusal);
+    else pack_write_header(head, mine.h);
+
+    if (local && N > 1 && !root) {   // the offer: the root's call pulls it
+        Offer& o = v.offer;
+        o.state = Offer::None;
+        if (!o.ev) HIPCHK(c, hipEventCreateWithFlags(&o.ev, hipEventDisableTiming));
+        std::memcpy(o.header, head, sizeof head);
+        o.cnt = mine.refusal ? nullptr : v.vdi.cnt;
+        o.dep = mine.s.dep;
+        o.col = mine.s.col;
+        HIPCHK(c, hipEventRecord(o.ev, v.stream));
+        o.state = Offer::Made;
+        if (wire_bytes && !mine.refusal) *wire_bytes = gather_section_bytes(mine.lay);
+        return 0;
+    }
+
+    // 1. the offer: every rank's header
+    const size_t verdict_at = (size_t)(root ? N : 1) * kPackHeaderBytes;
+    if (rccl) {
+        int rc = 0;
+        if ((rc = v.gm_ctl.reserve(c, (size_t)kPackSetMax * kPackHeaderBytes + sizeof(GatherVerdict))) ||
+            (rc = v.h_gm_ctl.reserve(c, (size_t)kPackSetMax * kPackHeaderBytes + sizeof(GatherVerdict))))
+            return rc;
+    }
+    if (!root) {   // a peer over RCCL
+        std::memcpy(v.h_gm_ctl.get(), head, sizeof head);
+        HIPCHK(c, hipMemcpyAsync(v.gm_ctl.get(), v.h_gm_ctl.get(), sizeof head, hipMemcpyHostToDevice, v.stream));
+        NCCLCHK(c, ncclGroupStart());
+        NCCLCHK(c, ncclSend(v.gm_ctl.get(), sizeof head, ncclUint8, 0, c->comm, v.stream));
+        NCCLCHK(c, ncclGroupEnd());
+        // (the offer has left before the wait for the root's answer is enqueued: nothing that a peer's progress
+        // depends on is ever queued behind a wait)
+        HIPCHK(c, hipStreamSynchronize(v.stream));
+        // 2. the verdict
+        NCCLCHK(c, ncclGroupStart());
+        NCCLCHK(c, ncclRecv(v.gm_ctl + verdict_at, sizeof(GatherVerdict), ncclUint8, 0, c->comm, v.stream));
+        NCCLCHK(c, ncclGroupEnd());
+        HIPCHK(c, hipMemcpyAsync(v.h_gm_ctl + verdict_at, v.gm_ctl + verdict_at, sizeof(GatherVerdict), hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(c, hipStreamSynchronize(v.stream));
+        GatherVerdict verdict;
+        std::memcpy(&verdict, v.h_gm_ctl + verdict_at, sizeof verdict);
+        if (verdict.reason != kGatherAccepted) return gather_rejected(c, who, verdict.rank, verdict.reason);
+        // 3. the payload (an empty section is not sent)
+        NCCLCHK(c, ncclGroupStart());
+        NCCLCHK(c, ncclSend(v.vdi.cnt, (size_t)mine.lay.px, ncclUint8, 0, c->comm, v.stream));
+        if (mine.h.E > 0) {
+            NCCLCHK(c, ncclSend(mine.s.dep, mine.lay.depth_bytes, ncclUint8, 0, c->comm, v.stream));
+            NCCLCHK(c, ncclSend(mine.s.col, mine.lay.colour_bytes, ncclUint8, 0, c->comm, v.stream));
+        }
+        NCCLCHK(c, ncclGroupEnd());
+        HIPCHK(c, hipStreamSynchronize(v.stream));
+        if (wire_bytes) *wire_bytes = gather_section_bytes(mine.lay);
+        return 0;
+    }
+
+    // the root (N = 1: the only rank)
+    unsigned char local_heads[kPackSetMax * kPackHeaderBytes];
+    unsigned char* heads = local_heads;
+    Offer offers[kPackSetMax];
+    if (rccl) {
+        heads = v.h_gm_ctl.get();
+        NCCLCHK(c, ncclGroupStart());
+        for (int p = 1; p < N; ++p)
+            NCCLCHK(c, ncclRecv(v.gm_ctl + (size_t)p * kPackHeaderBytes, kPackHeaderBytes, ncclUint8, p, c->comm, v.stream));
+        NCCLCHK(c, ncclGroupEnd());
+        HIPCHK(c, hipMemcpyAsync(heads, v.gm_ctl.get(), (size_t)N * kPackHeaderBytes, hipMemcpyDeviceToHost, v.stream));
+        HIPCHK(c, hipStreamSynchronize(v.stream));
+    } else if (N > 1) {
+        for (int p = 1; p < N; ++p) {
+            const insitu_ctx* q = c->group->ranks[p];
+            const std::string rank = std::string(who) + ": local group rank " + std::to_string(p);
+            if (!q) return fail(c, -1, rank + " missing");
+            if (q->view.offer.state == Offer::None) return fail(c, -1, rank + " has not offered (the peers call first, the root last)");
+            if (q->view.offer.state == Offer::Withdrawn) return fail(c, -1, rank + " has bound or packed since its offer");
+        }
+        for (int p = 1; p < N; ++p) {   // consumed, whatever comes of them
+            Offer& o = c->group->ranks[p]->view.offer;
+            offers[p] = o;
+            o.state = Offer::None;
+            std::memcpy(heads + (size_t)p * kPackHeaderBytes, o.header, kPackHeaderBytes);
+        }
+    }
+    std::memcpy(heads, head, sizeof head);
+
+    // 2. the verdict, once the root has room for what an accepted set sends
+    PackHeader h[kPackSetMax];
+    PackLayout lay[kPackSetMax];
+    PackSetStage at[kPackSetMax];
+    GatherVerdict verdict{};
+    int index = -1;
+    verdict.reason = pack_header_set_check(heads, N, h, lay, &index);
+    verdict.rank = index;
+    if (verdict.reason == kGatherAccepted) {
+        if (int rc = view_set_reserve(c, who, lay, N, at)) {
+            if (!rccl) return rc;
+            verdict.reason = kGatherAllocationFailed;
+            verdict.rank = 0;
+        }
+    }
+    if (rccl) {
+        std::memcpy(heads + verdict_at, &verdict, sizeof verdict);
+        HIPCHK(c, hipMemcpyAsync(v.gm_ctl + verdict_at, heads + verdict_at, sizeof verdict, hipMemcpyHostToDevice, v.stream));
+        NCCLCHK(c, ncclGroupStart());
+        for (int p = 1; p < N; ++p)
+            NCCLCHK(c, ncclSend(v.gm_ctl + verdict_at, sizeof verdict, ncclUint8, p, c->comm, v.stream));
+        NCCLCHK(c, ncclGroupEnd());
+        if (verdict.reason != kGatherAccepted) HIPCHK(c, hipStreamSynchronize(v.stream));
+    }
+    if (verdict.reason != kGatherAccepted) return gather_rejected(c, who, verdict.rank, verdict.reason);
+
+    // 3. the payload: the root's own stream into slot 0, before the bind reuses the buffers it lies in ...
+    unsigned char* const sg = v.ps_stage.get();
+    HIPCHK(c, hipMemcpyAsync(sg + at[0].cnt_at, v.vdi.cnt, (size_t)lay[0].px, hipMemcpyDeviceToDevice, v.stream));
+    if (h[0].E > 0) {
+        HIPCHK(c, hipMemcpyAsync(sg + at[0].dep_at, mine.s.dep, lay[0].depth_bytes, hipMemcpyDeviceToDevice, v.stream));
+        HIPCHK(c, hipMemcpyAsync(sg + at[0].col_at, mine.s.col, lay[0].colour_bytes, hipMemcpyDeviceToDevice, v.stream));
+    }
+    // ... and every peer's at its place (an empty section is not sent)
+    unsigned long long wire = 0;
+    if (rccl) NCCLCHK(c, ncclGroupStart());
+    for (int p = 1; p < N; ++p) {
+        wire += gather_section_bytes(lay[p]);
+        if (rccl) {
+            NCCLCHK(c, ncclRecv(sg + at[p].cnt_at, (size_t)lay[p].px, ncclUint8, p, c->comm, v.stream));
+            if (h[p].E > 0) {
+                NCCLCHK(c, ncclRecv(sg + at[p].dep_at, lay[p].depth_bytes, ncclUint8, p, c->comm, v.stream));
+                NCCLCHK(c, ncclRecv(sg + at[p].col_at, lay[p].colour_bytes, ncclUint8, p, c->comm, v.stream));
+            }
+        } else {
+            const Offer& o = offers[p];
+            HIPCHK(c, hipStreamWaitEvent(v.stream, o.ev, 0));   // the peer's pack, its stream
+            HIPCHK(c, hipMemcpyAsync(sg + at[p].cnt_at, o.cnt, (size_t)lay[p].px, hipMemcpyDeviceToDevice, v.stream));
+            if (h[p].E > 0) {
+                HIPCHK(c, hipMemcpyAsync(sg + at[p].dep_at, o.dep, lay[p].depth_bytes, hipMemcpyDeviceToDevice, v.stream));
+                HIPCHK(c, hipMemcpyAsync(sg + at[p].col_at, o.col, lay[p].colour_bytes, hipMemcpyDeviceToDevice, v.stream));
+            }
+        }
+    }
+    if (rccl) NCCLCHK(c, ncclGroupEnd());
+    HIPCHK(c, hipStreamSynchronize(v.stream));
+    if (wire_bytes) *wire_bytes = wire;
+
+    // 4. the bind: from here on the root's own VDI is a stream among the others
+    view_unbind(v);
+    if (N == 1)
+        return view_bind_packed_parsed(c, who, -1, h[0], lay[0],
+                                       {sg + at[0].cnt_at, sg + at[0].dep_at, sg + at[0].col_at, hipMemcpyDeviceToDevice});
+    return view_set_bind(c, who, h, lay, at, N);
+}
+
+}  // namespace
+
+int insitu_view_gather_merged(insitu_ctx* c, int format, unsigned long long* wire_bytes) {
+    const char* who = "insitu_view_gather_merged";
+    if (!c) return fail(nullptr, -1, std::string(who) + ": null context");
+    if (wire_bytes) *wire_bytes = 0;
+    const int rc = c->N > kPackSetMax
+                       ? fail(c, -1, std::string(who) + ": " + std::to_string(c->N) + " ranks, at most " + std::to_string(kPackSetMax))
+                       : view_gather(c, format, wire_bytes, who);
+    if (rc != 0 && is_root(c)) view_unbind(c->view);   // (a failed bind leaves no VDI bound)
+    return rc;
 }
 
 int insitu_view_render(insitu_ctx* c, const insitu_camera* cam, int out_w, int out_h, void* host_out, size_t cap) {

@@ -147,6 +147,96 @@ inline bool pack_set_stage(const PackLayout* layouts, int n, PackSetStage* at, s
     return true;
 }
 
+// ---- the headers of a gather (insitu_view_gather_merged) ----
+// Before any section moves, the root of a gather holds every rank's header and nothing else of its stream.  A rank
+// that cannot take part offers a refusing header instead: zeroed magic, and its reason where the version would be.
+// The verdict names one rank and one of these codes on every rank.
+enum PackGatherReason : uint32_t {
+    kGatherAccepted = 0,
+    // a rank's own refusal
+    kGatherNothingBound = 1,
+    kGatherBadFormatArgument = 2,
+    kGatherFrameInFlight = 3,
+    kGatherAllocationFailed = 4,
+    // what the root finds in a header: pack_parse's reasons ...
+    kGatherBadMagic = 5,
+    kGatherUnknownVersion = 6,
+    kGatherUnknownFormat = 7,
+    kGatherZeroWindow = 8,
+    kGatherBadSlots = 9,
+    kGatherOutOfRange = 10,
+    // ... and pack_set_parse's
+    kGatherWindowDiffers = 11,
+    kGatherCameraDiffers = 12,
+    kGatherBadRankCount = 13,
+    kGatherRejectedHeader = 14,   // (a reason of pack_parse's that has no code of its own)
+    kGatherReasons
+};
+constexpr uint32_t kGatherLastRefusal = kGatherAllocationFailed;
+
+inline const char* pack_gather_reason_text(uint32_t reason) {
+    switch (reason) {
+    case kGatherAccepted: return "accepted";
+    case kGatherNothingBound: return "no VDI bound (insitu_view_bind first)";
+    case kGatherBadFormatArgument: return "bad format argument";
+    case kGatherFrameInFlight: return "a pipelined frame is in flight (insitu_pipeline_flush first)";
+    case kGatherAllocationFailed: return "a device allocation failed";
+    case kGatherBadMagic: return "bad magic";
+    case kGatherUnknownVersion: return "unknown version";
+    case kGatherUnknownFormat: return "unknown format";
+    case kGatherZeroWindow: return "W and H must be > 0";
+    case kGatherBadSlots: return "S must be in [1,255]";
+    case kGatherOutOfRange: return "dimensions or entry count out of range";
+    case kGatherWindowDiffers: return "W and H differ from rank 0's";
+    case kGatherCameraDiffers: return "the generating camera differs from rank 0's";
+    case kGatherBadRankCount: return "needs 1 to 32 ranks";
+    case kGatherRejectedHeader: return "header rejected";
+    default: return "unknown reason";
+    }
+}
+
+inline void pack_write_refusal(void* out, uint32_t reason) {
+    unsigned char b[kPackHeaderBytes] = {};
+    memcpy(b + 4, &reason, 4);
+    memcpy(out, b, sizeof b);
+}
+
+// n headers of kPackHeaderBytes each, one behind the other, with no stream bodies: kGatherAccepted when n is
+// 1..kPackSetMax, no header refuses, every header passes what pack_parse checks of one -- given the size the header
+// itself implies -- and all have header 0's W, H and pv_g (the 64 bytes compared as they are); else the reason, with
+// *index the header it lies with (-1: the set itself).  A refusing header is reported with the reason it carries.
+// headers_out and layouts have room for kPackSetMax entries; those before *index are filled in.
+inline uint32_t pack_header_set_check(const void* headers, int n, PackHeader* headers_out, PackLayout* layouts, int* index) {
+    *index = -1;
+    if (!headers || n < 1 || n > kPackSetMax) return kGatherBadRankCount;
+    const unsigned char* b = static_cast<const unsigned char*>(headers);
+    const unsigned char no_magic[4] = {};
+    for (int j = 0; j < n; ++j, b += kPackHeaderBytes) {
+        *index = j;
+        uint32_t word;
+        memcpy(&word, b + 4, 4);
+        if (memcmp(b, no_magic, 4) == 0 && word >= 1 && word <= kGatherLastRefusal) return word;
+        // the size a stream of this header has, where its fields give one (where they do not, pack_parse names the
+        // field before it comes to the size)
+        PackHeader& h = headers_out[j];
+        memcpy(&h.format, b + 8, 4);
+        memcpy(&h.W, b + 12, 4);
+        memcpy(&h.H, b + 16, 4);
+        memcpy(&h.S, b + 20, 4);
+        memcpy(&h.E, b + 24, 8);
+        const size_t bytes = pack_layout(h.format, h.W, h.H, h.S, h.E, &layouts[j]) ? layouts[j].total : kPackHeaderBytes;
+        if (const char* why = pack_parse(b, bytes, &h, &layouts[j])) {
+            for (uint32_t r = kGatherBadMagic; r <= kGatherOutOfRange; ++r)
+                if (strcmp(why, pack_gather_reason_text(r)) == 0) return r;
+            return kGatherRejectedHeader;
+        }
+        if (h.W != headers_out[0].W || h.H != headers_out[0].H) return kGatherWindowDiffers;
+        if (memcmp(h.pv_g, headers_out[0].pv_g, sizeof h.pv_g) != 0) return kGatherCameraDiffers;
+    }
+    *index = -1;
+    return kGatherAccepted;
+}
+
 // binary32 -> binary16, round to nearest even, by integer operations (numpy's astype(float16), bit for bit:
 // subnormal halves are produced, anything that rounds beyond 65504 is infinity, a NaN keeps its top payload bits
 // and stays a NaN).  Independent of the kernel's rounding and denormal modes.  gfx950's own conversion gives the

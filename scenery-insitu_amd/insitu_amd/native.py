@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "insitu_set_option", "insitu_read_region", "insitu_frame_pipelined", "insitu_pipeline_flush",
     "insitu_view_bind", "insitu_view_bind_host", "insitu_view_bind_host_set", "insitu_view_render",
     "insitu_view_pack_bytes", "insitu_view_pack", "insitu_view_bind_packed", "insitu_view_bind_packed_set",
+    "insitu_view_gather_merged",
 )
 
 # enum insitu_option
@@ -144,6 +145,7 @@ def load() -> ctypes.CDLL:
         "insitu_view_pack": (i, [vp, i, vp, sz, ctypes.POINTER(sz)]),
         "insitu_view_bind_packed": (i, [vp, vp, sz]),
         "insitu_view_bind_packed_set": (i, [vp, ctypes.POINTER(vp), ctypes.POINTER(sz), i]),
+        "insitu_view_gather_merged": (i, [vp, i, ctypes.POINTER(ctypes.c_ulonglong)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -334,6 +334,15 @@ class InSituContext:
         sizes = (ctypes.c_size_t * max(n, 1))(*[b.nbytes for b in bs])
         self._check(self.lib.insitu_view_bind_packed_set(self.h, ptrs, sizes, n), "insitu_view_bind_packed_set")
 
+    def view_gather_merged(self, fmt: int = native.PACK_FLOAT) -> int:
+        """Gather every rank's bound VDI into one merged VDI bound on rank 0, device to device: what
+        view_bind_packed_set binds from the ranks' view_pack(fmt) streams in rank order.  A collective (in a local
+        group: the peers call first, the root last); not with a pipelined frame in flight.  -> the section bytes
+        this rank sent (a peer) or received (the root); 0 with one rank."""
+        wire = ctypes.c_ulonglong(0)
+        self._check(self.lib.insitu_view_gather_merged(self.h, int(fmt), ctypes.byref(wire)), "insitu_view_gather_merged")
+        return int(wire.value)
+
     def stats(self) -> dict:
         """insitu_stats as a dictionary, one key per field of native.Stats: the last frame's times and counters, and
         of the bound VDI view_slots, view_overlaps, view_entries (its stored entries), view_bytes (device bytes of

@@ -36,9 +36,17 @@ path, insitu_view_bind_host_set of the same eight sub-VDIs read back dense: for 
 bytes staged, ms_view_bind and the wall time of the call, one warm-up and the best of three.  Prints one JSON line and
 nothing else runs.
 
+--gather-merged: the whole scene on rank 0 without the host.  Config 2 as a local group of 8
+one-brick ranks on this one GPU; every rank binds its sub-VDI and insitu_view_gather_merged gathers them on rank 0, in
+both formats: the call's wall time on the root (the peers' calls, which pack and offer, beside it), ms_view_bind and
+the wire bytes -- on one GPU the "wire" is a device-to-device copy; over xGMI it is unmeasured.  For comparison the
+same frame through the host: insitu_view_pack on every rank and insitu_view_bind_packed_set on rank 0.  The FLOAT pack
+of both results must be equal byte for byte.  Prints one JSON line and nothing else runs.
+
 usage: python tools/view_bench.py [--brick 512] [--sim-n 512] [--views 36] [--passes 3] [--count-views 2] [--pack] [--compact]
        python tools/view_bench.py --merged [--compact] [--brick 512] [--sim-n 512] [--views 36] [--passes 2]
        python tools/view_bench.py --packed-set [--compact] [--brick 512] [--sim-n 512]
+       python tools/view_bench.py --gather-merged [--compact] [--brick 512] [--sim-n 512]
 """
 from __future__ import annotations
 
@@ -261,6 +269,92 @@ def run_packed_set(args):
     print(json.dumps(res))
 
 
+def run_gather_merged(args):
+    """--gather-merged: config 2 as 8 one-brick ranks of a local group, gathered on rank 0 device to device."""
+    from insitu_amd import native, scene
+    from insitu_amd.renderer import InSituContext, LocalGroup
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    n = args.brick
+    bricks = scene.grid_bricks(n * 2, 2)
+    nr = len(bricks)
+    t0 = time.perf_counter()
+    group = LocalGroup(nr)
+    ctxs = []
+    for r, (origin, vw, _) in enumerate(bricks):
+        ctx = InSituContext(W_IMG, H_IMG, max_supersegments=S, bricks_per_rank=1, rank=r, nranks=nr, local_group=group,
+                            keep_passes=False)
+        ctx.set_transfer(scene.transfer_function(), scene.colormap_hot(), conv_scale=1.0 / 0.5, conv_offset=0.0)
+        v = scene.gray_scott(n, steps=1500, seed=1000 + r, device=dev, sim_n=min(args.sim_n, n)).contiguous()
+        ctx.set_brick(0, v, scene.brick_model(origin, vw), dtype=native.F32)
+        del v
+        ctxs.append(ctx)
+    cam = scene.orbit_camera(W_IMG, H_IMG, yaw_deg=30.0, pitch_deg=20.0, voxel_world=bricks[0][1])
+    for stage in ("render", "exchange", "composite"):
+        for ctx in ctxs:
+            getattr(ctx, stage)(*((cam,) if stage == "render" else ()))
+    for ctx in ctxs[::-1]:
+        ctx.gather(want_image=False)
+    torch.cuda.synchronize()
+    log(f"view_bench: {nr} ranks of one {n}^3 brick and their frame in {time.perf_counter() - t0:.1f} s")
+    root = ctxs[0]
+    formats = (("float", native.PACK_FLOAT), ("half", native.PACK_HALF))
+    layouts = {"dense": 0, "compact": 1} if args.compact else {"dense": 0}
+    res = {"metric": f"insitu_view_gather_merged of config 2 ({W_IMG}x{H_IMG}, S = {S}, {nr}x{n}^3 volume) as a local group of "
+                     f"{nr} one-brick ranks on one GPU, against insitu_view_pack on every rank + insitu_view_bind_packed_set",
+           "timing": "one warm-up, then the best of three; ms_view_bind: HIP events around the root's bind kernels; wall: the "
+                     "calls as the host sees them.  One GPU: the wire is a device-to-device copy; xGMI is unmeasured",
+           "gather_merged": {}, "through_the_host": {}}
+    for lname, layout in layouts.items():
+        for ctx in ctxs:
+            ctx.set_option(native.OPT_VIEW_COMPACT, layout)
+        for fname, fmt in formats:
+            wall_root, wall_peers, ms_bind, wire = [], [], [], 0
+            for _ in range(4):
+                for ctx in ctxs:
+                    ctx.view_bind(native.VIEW_MERGED)
+                t0 = time.perf_counter()
+                sent = [ctx.view_gather_merged(fmt) for ctx in ctxs[1:]]
+                t1 = time.perf_counter()
+                wire = root.view_gather_merged(fmt)
+                wall_root.append((time.perf_counter() - t1) * 1e3)
+                wall_peers.append((t1 - t0) * 1e3)
+                ms_bind.append(root.stats()["ms_view_bind"])
+                assert wire == sum(sent)
+            st = root.stats()
+            gathered = {f: root.view_pack(f2) for f, f2 in formats}
+            r = {"ms_wall_root": min(wall_root[1:]), "ms_wall_root_first": wall_root[0], "ms_wall_peers": min(wall_peers[1:]),
+                 "ms_view_bind": min(ms_bind[1:]), "wire_bytes": int(wire), "view_slots": int(st["view_slots"]),
+                 "view_entries": int(st["view_entries"]), "view_overlaps": int(st["view_overlaps"]),
+                 "view_layout_bytes": int(st["view_bytes"])}
+            res["gather_merged"][f"{lname}_{fname}"] = r
+            log(f"view_bench: gather {lname} {fname} {json.dumps(r)}")
+            # the same frame through the host: every rank packs, the root binds the set
+            wall_pack, wall_set, ms_set = [], [], []
+            for _ in range(4):
+                for ctx in ctxs:
+                    ctx.view_bind(native.VIEW_MERGED)
+                t0 = time.perf_counter()
+                streams = [ctx.view_pack(fmt) for ctx in ctxs]
+                t1 = time.perf_counter()
+                root.view_bind_packed_set(streams)
+                wall_set.append((time.perf_counter() - t1) * 1e3)
+                wall_pack.append((t1 - t0) * 1e3)
+                ms_set.append(root.stats()["ms_view_bind"])
+            for f, f2 in formats:
+                assert np.array_equal(root.view_pack(f2), gathered[f]), "the gather differs from the set bind of the ranks' streams"
+            h = {"ms_wall_pack_all_ranks": min(wall_pack[1:]), "ms_wall_bind_packed_set": min(wall_set[1:]),
+                 "ms_view_bind": min(ms_set[1:]), "host_bytes": sum(int(x.size) for x in streams)}
+            res["through_the_host"][f"{lname}_{fname}"] = h
+            log(f"view_bench: through the host {lname} {fname} {json.dumps(h)}")
+            del streams, gathered
+    for ctx in ctxs:
+        ctx.close()
+    group.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--brick", type=int, default=512)
@@ -279,9 +373,13 @@ def main():
                     help="INSITU_VIEW_MERGED of the flatten context against INSITU_VIEW_GATHERED of the composite_vdi one")
     ap.add_argument("--packed-set", action="store_true",
                     help="insitu_view_bind_packed_set of the eight packed sub-VDIs against insitu_view_bind_host_set")
+    ap.add_argument("--gather-merged", action="store_true",
+                    help="insitu_view_gather_merged over a local group of 8 one-brick ranks against pack + bind_packed_set")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("view_bench: needs a GPU (timings are HIP-event times of the kernel)")
+    if args.gather_merged:
+        return run_gather_merged(args)
     if args.packed_set:
         return run_packed_set(args)
     if args.merged:
