@@ -167,7 +167,7 @@ int create_slot_events(insitu_ctx* c, FrameSlot& f) {
 }
 
 // allocate one frame slot's generator buffers (VDI mode): send blocks, octree counters, pass counts, pending
-// counts and step counts, generator counters, and -- with a sample cache of `chunks` 32-byte units -- the
+// counts and supersegment records, generator counters, and -- with a sample cache of `chunks` 32-byte units -- the
 // cache, the search queue, the pinned counter copy and the tile-order keys; plus the slot's events
 int alloc_slot(insitu_ctx* c, FrameSlot& f, size_t chunks) {
     int rc = 0;
@@ -177,7 +177,7 @@ int alloc_slot(insitu_ctx* c, FrameSlot& f, size_t chunks) {
     if ((rc = f.vcol_send.alloc(c, sendE)) || (rc = f.vdep_send.alloc(c, sendE))) return rc;
     const size_t oct = (size_t)c->BV * (size_t)c->S * (size_t)c->ncx * (size_t)c->ncy;
     if ((rc = f.octree.alloc(c, oct ? oct : 1))) return rc;
-    if ((rc = f.seg_pending.alloc(c, px)) || (rc = f.seg_steps.alloc(c, sendE))) return rc;
+    if ((rc = f.seg_pending.alloc(c, px)) || (rc = f.seg_rec.alloc(c, sendE))) return rc;
     // per-pixel supersegment counts: empty until the first render (the slots are not zero-filled)
     if (hipMemset(f.seg_pending, 0, sizeof(uint16_t) * px) != hipSuccess)
         return fail(c, -3, "hipMemset of the supersegment counts failed");
@@ -750,7 +750,7 @@ int render_frame(insitu_ctx* c, FrameSlot& f, const FrameCamera& cam, const Rend
         p.passes = f.passes;
         p.passes_stride = (size_t)c->W * (size_t)c->H;
         p.seg_pending = f.seg_pending;
-        p.seg_steps = f.seg_steps;
+        p.seg_rec = f.seg_rec;
         p.ncx = c->ncx; p.ncy = c->ncy;
         p.interval_size = (20.0f - 0.1f) / (float)c->S;   // VDIGenerator.comp:241-247
         p.cache = f.cache;

@@ -180,7 +180,7 @@ struct FrameSlot {
     DevBuf<uint32_t> octree;
     DevBuf<uint8_t> passes;
     DevBuf<uint16_t> seg_pending;       // per brick and pixel: supersegments awaiting vdi_finish_kernel
-    DevBuf<uint16_t> seg_steps;         // per sub-VDI entry: step count of a deferred colour
+    DevBuf<SegRecord> seg_rec;          // per sub-VDI entry: the stored supersegment of a deferred ray (32 bytes)
     DevBuf<GenCounters> counters;       // cache cursor + search queue counters
     DevBuf<PendingRay> queue;           // rays queued for the search kernel (B*W*H)
     DevBuf<float> cache;                // per-sample raymarch cache (32-byte chunks of 4 samples)

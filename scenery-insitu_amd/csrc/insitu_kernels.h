@@ -74,6 +74,18 @@ struct GenCounters {
     unsigned long long pipe_seq;
 };
 
+// A stored supersegment of a deferred ray, as vdi_search_kernel leaves it for vdi_finish_kernel: the raw
+// curV, the ray parameters of its boundaries and its step count, in one 32-byte sector (two 16-byte stores
+// through one pointer).  Indexed like the colour entries; records past a pixel's final count are stale
+// (speculative stores, earlier frames) and never read.
+struct alignas(32) SegRecord {
+    float4 curV;
+    float s0, e1;      // ray parameters of the opening sample and one step past the last non-transparent one
+    uint32_t steps;
+    uint32_t unused;
+};
+static_assert(sizeof(SegRecord) == 32, "SegRecord is one 32-byte sector");
+
 struct VdiGenParams {
     BrickDesc bricks[kMaxBricks];  // all local bricks; blockIdx.y selects one (or: the volumes of one VDI)
     int nvolumes;                  // > 0: bricks[0..nvolumes) are the volumes of ONE VDI (B == 1)
@@ -93,9 +105,9 @@ struct VdiGenParams {
     uint8_t* passes;    // H*W pass counts of brick 0 (may be null); brick b at + b*passes_stride
     uint16_t* seg_pending;  // H*W per brick (passes_stride): kPendingCount bits = supersegments stored
                             // for the pixel (<= S); | kPendingDeferred when their colours are raw curV
-                            // (see seg_steps); | kPendingCounted when their octree cells are counted
+                            // (see seg_rec); | kPendingCounted when their octree cells are counted
                             // already (otherwise vdi_finish_kernel counts them)
-    uint16_t* seg_steps;    // per supersegment entry (color's layout): step count of a deferred colour
+    SegRecord* seg_rec;     // per supersegment entry (color's layout): the stored supersegment of a deferred ray
     float* cache;       // per-sample cache in 32-byte chunks of 4 samples {LUT coord x4, opacity x4}
                         // (merged volumes: 64-byte slots of two chunk units, with the 4 samples'
                         // step indices, vdi_generate.hip MergedChunkStore); null = off

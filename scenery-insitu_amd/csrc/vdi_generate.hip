@@ -1181,7 +1181,7 @@ __device__ __forceinline__ void sample_tile(const VdiGenParams& P, const float* 
     unsigned long long base = 0;
     uint32_t total = 0;
     if (P.cache) {
-        // (a cached ray's supersegment step counts fit the 16-bit seg_steps entries)
+        // (rays of 65536 steps and more are searched in place; merged volumes keep step indices in 16 bits)
         const uint32_t need = (valid && R.hit && R.numSteps < 65536) ? ((uint32_t)R.numSteps + 3u) >> 2 : 0u;
         // lane-interleaved (chunk_off): chunk c of lane l at base + c*64 + l, so the 64 lanes storing their chunk c
         // write 2 KiB in one piece (the wave takes 64 x its longest ray's chunks)
@@ -1394,8 +1394,12 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
     float step_first = 0.0f;         // ray parameter of the first cached sample
     bool last_final = false;         // the last cached sample is the ray's last sample
     f4 wfront{}, wback{};            // world-space ray (VDIGenerator.comp:289-290)
-    size_t e0 = 0;                   // entry of slot 0 of the pixel's output block (ray_out)
-    const size_t slot_stride = (size_t)P.H * 8;
+    // the record the lane's next stored supersegment goes to (an address: it steps with the count, past the
+    // pixel's S slots too, where nothing is stored); slot 0 of the pixel's block (ray_out) when a pass starts
+    uintptr_t rec = 0;
+    // slot to slot of a pixel (a scalar: held in a vector register it saved two v_readlane per stored record,
+    // and the merged-volume kernel spilled vector registers)
+    const uint32_t rec_stride = (uint32_t)P.H * 8u * (uint32_t)sizeof(SegRecord);
     Search q{};                      // root of the group's current round (identical in all its lanes)
     Thr th{};                        // the decision thresholds of this lane's tree node (or of the final pass)
     SegState st;
@@ -1424,7 +1428,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
             wfront = R.wfront;
             wback = R.wback;
         }
-        e0 = (size_t)(ray_out(P, gx, gy, (int)bslot).color - P.color);
+        rec = reinterpret_cast<uintptr_t>(P.seg_rec + (ray_out(P, gx, gy, (int)bslot).color - P.color));
         const float4* cbase = reinterpret_cast<const float4*>(P.cache) + 2 * (size_t)chunk;
         n = (int)pr.n;
         nchunks = (n + 3) >> 2;
@@ -1523,8 +1527,9 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
                     home = __shfl(home, src);
                     wfront = f4{__shfl(wfront.x, src), __shfl(wfront.y, src), __shfl(wfront.z, src), __shfl(wfront.w, src)};
                     wback = f4{__shfl(wback.x, src), __shfl(wback.y, src), __shfl(wback.z, src), __shfl(wback.w, src)};
-                    e0 = (size_t)(uint32_t)__shfl((int)(uint32_t)e0, src) |
-                         ((size_t)(uint32_t)__shfl((int)(uint32_t)(e0 >> 32), src) << 32);
+                    // (the old leader waits at a round start: its record pointer is at slot 0)
+                    rec = (uintptr_t)(uint32_t)__shfl((int)(uint32_t)rec, src) |
+                          ((uintptr_t)(uint32_t)__shfl((int)(uint32_t)(rec >> 32), src) << 32);
                     if (lane == 0) atomicAdd(&ctr->regroups, 1u);
                     d = dn;
                     G = Gn;
@@ -1584,14 +1589,17 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
             const bool store = (q.written || q.iter + 1 >= spec_from) && node == 0;
             auto emit = [&](float s0, float e1, const f4& cv, int steps) {
                 if (store) {
-                    // stored supersegments: raw curV + step count, adjusted colour and octree cells
-                    // done afterwards (vdi_finish_kernel); the ones past S are not stored, their
-                    // cells are counted here (:132-180)
+                    // stored supersegments: one record of raw curV, boundaries and step count through the
+                    // running pointer; adjusted colour, NDC depths and octree cells done afterwards
+                    // (vdi_finish_kernel); the ones past S are not stored, their cells are counted here (:132-180)
                     if (nseg < S) {
-                        const size_t e = e0 + (size_t)nseg * slot_stride;
-                        P.color[e] = make_float4(cv.x, cv.y, cv.z, cv.w);
-                        P.depth[e] = make_float2(s0, e1);
-                        P.seg_steps[e] = (uint16_t)steps;
+                        // (the address went through integer registers: name its address space, or the
+                        // stores are flat ones)
+                        typedef float v4f __attribute__((ext_vector_type(4)));
+                        typedef __attribute__((address_space(1))) v4f global_v4f;
+                        global_v4f* const r = reinterpret_cast<global_v4f*>(rec);
+                        r[0] = v4f{cv.x, cv.y, cv.z, cv.w};
+                        r[1] = v4f{s0, e1, __uint_as_float((uint32_t)steps), 0.0f};
                     } else if (write) {   // (s0, e1: ray parameters, as stored)
                         const int gy = (int)(pix / (uint32_t)P.W), gx = (int)(pix - (uint32_t)gy * (uint32_t)P.W);
                         Ray R;
@@ -1601,6 +1609,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
                                       R.cy);
                     }
                     nseg++;
+                    rec += rec_stride;
                 }
             };
             // a search pass that has closed more than S supersegments is decided (the walk only asks
@@ -1716,6 +1725,7 @@ __device__ __forceinline__ void search_loop(const VdiGenParams& P, float4* smem)
                     th = search_thr(sq_threshold(q.found ? q.mid : tree_threshold(q.low, q.high, q.mid, node)), P.xfer.cmag, q);
                     st.reset();
                     k = 0;
+                    rec -= (uintptr_t)(uint32_t)nseg * rec_stride;   // back to slot 0: the pointer stepped with the count
                     nseg = 0;
                     stp = step_first;
                 }
@@ -1759,7 +1769,8 @@ __global__ __launch_bounds__(256, kSearchMinWaves) void vdi_search_kernel(const 
 constexpr int kFinishMinBlocks = 1;   // vdi_finish_kernel: waves per SIMD asked of the compiler
 // The stored supersegments the generator left pending: their octree cell counts
 // (AccumulateVDI.comp:143-177) and, for the search kernel's rays, their adjusted colours
-// (AccumulateVDI.comp:50-54, from the raw curV and step count stored in the slot).  One lane per
+// and NDC depths (AccumulateVDI.comp:50-54, from the raw curV, boundaries and step count of the slot's
+// SegRecord; the colour and depth entries of such a pixel are written here, not read).  One lane per
 // pixel, one wave per 8x8 tile of one brick.  Counting is order-independent and the colour is the
 // same function of the same operands, so the results are identical to doing both inline; done
 // here, the work runs with the lanes of a tile together instead of with the one lane closing a
@@ -1802,15 +1813,20 @@ __global__ __launch_bounds__(256, kFinishMinBlocks) void vdi_finish_kernel(const
         for (int i0 = 0; i0 < cnt; i0 += 4) {
             float2 se[4];
             float4 cv[4];
-            uint16_t st[4];
+            uint32_t st[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int i = i0 + u < cnt ? i0 + u : cnt - 1;   // (a repeated slot is read, not used)
                 const size_t e = e0 + (size_t)i * o.slot_stride;
-                se[u] = P.depth[e];
                 if (deferred) {
-                    cv[u] = P.color[e];
-                    st[u] = P.seg_steps[e];
+                    // the search kernel's record: the 64 records of a tile's slot are 2 KiB in one piece
+                    const float4* const r = reinterpret_cast<const float4*>(P.seg_rec + e);
+                    cv[u] = r[0];
+                    const float4 t = r[1];
+                    se[u] = make_float2(t.x, t.y);
+                    st[u] = __float_as_uint(t.z);
+                } else {
+                    se[u] = P.depth[e];
                 }
             }
 #pragma unroll
@@ -1819,7 +1835,7 @@ __global__ __launch_bounds__(256, kFinishMinBlocks) void vdi_finish_kernel(const
                 const size_t e = e0 + (size_t)(i0 + u) * o.slot_stride;
                 float2 d = se[u];
                 if (deferred) {
-                    // the generator stored the ray parameters of the boundaries: their NDC z
+                    // the record holds the ray parameters of the boundaries: their NDC z
                     // (AccumulateVDI.comp:214-217 at the opening sample, :243-248 one step past the
                     // last non-transparent one), and raw colours: adjusted here (:50-54)
                     d = make_float2(ndc_at(P, R.wfront, R.wback, d.x), ndc_at(P, R.wfront, R.wback, d.y));
@@ -1849,7 +1865,7 @@ __global__ __launch_bounds__(256, kFinishMinBlocks) void vdi_finish_kernel(const
 }
 
 hipError_t launch_vdi_finish(const VdiGenParams& p, hipStream_t s) {
-    if (!p.seg_pending || !p.seg_steps) return hipErrorInvalidValue;
+    if (!p.seg_pending || !p.seg_rec) return hipErrorInvalidValue;
     const int tiles = p.ytiles * p.nstrips * p.strip_tiles;
     hipLaunchKernelGGL(vdi_finish_kernel, dim3((tiles + 3) / 4, p.B), dim3(256), 4 * sizeof(uint32_t) * p.S, s, p);
     return hipGetLastError();
@@ -1910,7 +1926,7 @@ hipError_t launch_vdi_sample(const VdiGenParams& p, hipStream_t s) {
     const int tiles = p.ytiles * p.nstrips * p.strip_tiles;
     const dim3 grid((tiles + 3) / 4, p.B);
     const size_t lds = sample_lds_bytes(p.xfer.n_tf, p.xfer.n_cm);
-    if (p.B < 1 || p.B > kMaxBricks || !p.seg_pending || !p.seg_steps || !p.ctr) return hipErrorInvalidValue;
+    if (p.B < 1 || p.B > kMaxBricks || !p.seg_pending || !p.seg_rec || !p.ctr) return hipErrorInvalidValue;
     for (int b = 1; b < p.B; ++b)   // one voxel type per launch (the kernel is templated on it)
         if (p.bricks[b].dtype != p.bricks[0].dtype) return hipErrorInvalidValue;
     if (p.cache) {
