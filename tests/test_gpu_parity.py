@@ -600,7 +600,7 @@ def test_set_option_validation():
     sc = make_scene(n=16, W=32, H=24)
     with _ctx_for(sc, S=4) as ctx:
         for opt, bad in ((native.OPT_SEARCH_DEPTH, 7), (native.OPT_SEARCH_DEPTH, -1), (native.OPT_ROUND_BATCH, 0),
-                         (native.OPT_SEARCH_OVERSUB, 0), (native.OPT_EXACT_SEARCH, 2), (native.OPT_TILE_ORDER, 2),
+                         (native.OPT_ROUND_BATCH, 65), (native.OPT_LONG_SAMPLES, -1), (native.OPT_SEARCH_OVERSUB, 0), (native.OPT_EXACT_SEARCH, 2), (native.OPT_TILE_ORDER, 2),
                          (6, 0), (7, 0), (native.OPT_SUPER_TILE, 3), (native.OPT_REGROUP, 2), (native.OPT_EXACT_TILE_KEYS, 2),
                          (native.OPT_PIPE_TRIGGER, 3), (native.OPT_PIPE_OVERSUB, 0), (native.OPT_PIPE_OVERSUB, 65),
                          (native.OPT_PIPE_SEARCH_RAYS, -1), (native.OPT_PIPE_SEARCH_RAYS, (1 << 24) + 1),
