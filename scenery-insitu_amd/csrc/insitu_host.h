@@ -1,6 +1,7 @@
-// insitu_host.h -- private to the host side of libinsitu_hip.so: what insitu_hip.cpp (the frame) and
-// insitu_view.cpp (the novel-view subsystem) both need -- the owners of device memory, the error helpers, the
-// matrix helpers and the context with its frame slots and view state.
+// insitu_host.h -- private to the host side of libinsitu_hip.so: what insitu_context.cpp (the context's set-up and
+// inputs), insitu_hip.cpp (the frame's stages), insitu_read.cpp (readbacks and statistics) and insitu_view.cpp (the
+// novel-view subsystem) share -- the owners of device memory, the error helpers, the matrix helpers, the context
+// with its frame slots and view state, and the few functions one of those files defines for another.
 #pragma once
 
 #include "insitu_hip.h"
@@ -18,7 +19,6 @@
 using namespace insitu;
 
 // records msg as the context's error (no context: the calling thread's, read by insitu_last_error(NULL)); returns code
-
 int fail(insitu_ctx* c, int code, const std::string& msg);
 
 // Owner of one device allocation of `count()` elements (Pinned: of page-locked host memory), freed when it goes
@@ -225,9 +225,9 @@ struct ViewState {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float ms = 0.0f;                    // the last render's kernel
-    long long skip = 1;                 // INSITU_OPT_VIEW_SKIP
+    long long skip = 1;                 // insitu_set_option: the view-skip option
     // the compact view layout: vdi.loc != null says the bound VDI has it
-    long long compact_next = 0;         // INSITU_OPT_VIEW_COMPACT: the layout the next bind takes
+    long long compact_next = 0;         // insitu_set_option: the view layout the next bind takes
     DevBuf<uint16_t> loc;               // a pixel's entries before it in its block (vdi.boff is pk_boff)
     // the packed stream of the bound VDI (insitu_view_pack, insitu_view_bind_packed; vdi_pack.hip)
     bool counted = false;               // pk_boff and pk_E describe the bound VDI (once per bind; view_unbind clears it)
@@ -272,6 +272,13 @@ struct insitu_ctx {
     size_t blockE = 0;      // VDI entries per (strip, brick) block
     size_t plainBlock = 0;  // pixels per (strip, brick) block in plain mode
     size_t stripPx = 0;     // pixels of one composited strip
+    // sizes derived from the ones above, once, in insitu_create (VDI mode; plain mode: ytiles and framePx)
+    int ytiles = 0;         // 8-row tiles per column of tiles
+    size_t framePx = 0;     // pixels of the frame
+    size_t stripTiles = 0;  // tiles of one strip
+    size_t regionE = 0;     // VDI entries of one source's region: BV blocks
+    size_t sendE = 0;       // VDI entries of a slot's send buffers: N regions
+    size_t octreeN = 0;     // octree counters of a slot
     hipStream_t stream = nullptr;
     bool own_stream = false;
     ncclComm_t comm = nullptr;
@@ -287,7 +294,9 @@ struct insitu_ctx {
     DevBuf<uint32_t> d_pdep_send;
     DevBuf<uint32_t> d_pcol_recv;
     DevBuf<uint32_t> d_pdep_recv;
-    DevBuf<uint32_t> d_strip;
+    // the composited strips: N blocks [rank] on the root, one elsewhere.  This rank's own strip is the first block
+    // on every rank (the root is rank 0), so every stage writes and reads it at offset 0; the gather fills the
+    // root's other blocks
     DevBuf<uint32_t> d_gather;
     DevBuf<uint32_t> d_image;
     DevBuf<float4> d_ref_col;           // reference-layout staging for insitu_distribute_vdis: send | recv
@@ -320,14 +329,11 @@ struct insitu_ctx {
     bool composite_vdi = false;         // VDICompositor output instead of the RGBA flatten
     int S_out = 0;
     size_t cblockE = 0;                 // composited-VDI entries per strip block (S_out slots)
-    DevBuf<float4> d_cvdi_col;          // this rank's composited strip (non-root ranks)
-    DevBuf<float2> d_cvdi_dep;
-    DevBuf<float4> d_gvdi_col;          // root: gathered composited strips [rank][block]
-    DevBuf<float2> d_gvdi_dep;
+    DevBuf<float4> d_gvdi_col;          // the composited VDI strips, as d_gather: [rank][block] on the root, this
+    DevBuf<float2> d_gvdi_dep;          // rank's block alone elsewhere
     bool gvdi_valid = false;            // root: a gather has filled them, from the frame of camera gvdi_pv
     float gvdi_pv[16] = {};
-    DevBuf<uint16_t> d_cvdi_cnt;        // per pixel of this rank's composited strip: slots written (non-root ranks)
-    DevBuf<uint16_t> d_gvdi_cnt;        // root: the gathered counts [rank][y][x_local]
+    DevBuf<uint16_t> d_gvdi_cnt;        // per pixel of those strips: slots written [rank][y][x_local]
     DevBuf<uint8_t> d_cpasses;          // compositor search passes of the strip
     DevBuf<float4> d_cseq;              // VDICompositor merge cache (kCompEntryF4 float4 per entry)
     DevBuf<unsigned long long> d_cseq_cursor;
@@ -360,7 +366,7 @@ struct insitu_ctx {
     // in either order
     DevBuf<unsigned long long> pipe_flag;
     long long pipe_frames = 0;          // frame index of the next pipelined render
-    int pipe_trigger = 2;               // 0: after the previous search; 1: at its queue drain; 2: none (default:
+    long long pipe_trigger = 2;         // 0: after the previous search; 1: at its queue drain; 2: none (default:
                                         // the search keeps only the blocks its queue needs)
     bool pipe_wait_value = true;        // hipStreamWaitValue64 works here (else mode 1 falls back to 0)
     ViewState view;
@@ -381,7 +387,7 @@ struct insitu_ctx {
             return fail(ctx, -4, std::string(#expr " failed: ") + ncclGetErrorString(r_));         \
     } while (0)
 
-bool is_root(const insitu_ctx* c);
+inline bool is_root(const insitu_ctx* c) { return c->rank == 0; }
 
 // the completed frame's slot and the stream its readbacks run on: with a pipelined frame in flight the completion
 // stream (the context stream may be busy with work for the next frame, the completion stream holds nothing of it)
@@ -389,11 +395,25 @@ struct CompletedFrame {
     FrameSlot& f;
     hipStream_t s;
 };
-CompletedFrame completed_frame(const insitu_ctx* c);
+inline CompletedFrame completed_frame(const insitu_ctx* c) {
+    return {*c->cur, c->pipe_inflight ? c->pipe_comp : c->stream};
+}
 
 // after a synchronisation of the stream of slot f's last render: did a persistent kernel of that render hit its
 // wall-clock bound?
 int check_fault(insitu_ctx* c, FrameSlot& f);
+
+// after a synchronisation of the stream of slot f's last render: its cache demand (h_ctr) decides whether a
+// default-sized cache grows before the slot's next render (insitu_hip.cpp)
+void cache_observe(insitu_ctx* c, FrameSlot& f);
+
+// list v (source s = v / B, brick b = v % B) of this rank's strip, as the compositors read it: this rank's own
+// from slot f (insitu_hip.cpp)
+VdiList list_of(const insitu_ctx* c, const FrameSlot& f, int v);
+
+// the second frame slot, the sampling and completion streams and the trigger flag (first pipelined frame;
+// insitu_context.cpp)
+int pipeline_setup(insitu_ctx* c);
 
 // the view fields of insitu_get_stats (insitu_view.cpp)
 int view_stats(insitu_ctx* c, insitu_stats* out);

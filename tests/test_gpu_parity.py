@@ -596,19 +596,36 @@ def test_tile_order_bit_exact(order):
     assert np.count_nonzero(rd) > 0
 
 
+# every option of insitu_set_option with the ends of the range it accepts (include/insitu_hip.h); SUPER_TILE takes
+# the set {1, 2, 4} instead
+_OPTION_RANGES = (
+    (native.OPT_EXACT_SEARCH, 0, 1), (native.OPT_SEARCH_DEPTH, 0, 6), (native.OPT_LONG_SAMPLES, 0, 0xffffffff),
+    (native.OPT_ROUND_BATCH, 1, 64), (native.OPT_SEARCH_OVERSUB, 1, 64), (native.OPT_TILE_ORDER, 0, 1),
+    (native.OPT_SUPER_TILE, 1, 4), (native.OPT_REGROUP, 0, 1), (native.OPT_EXACT_TILE_KEYS, 0, 1),
+    (native.OPT_PIPE_TRIGGER, 0, 2), (native.OPT_PIPE_OVERSUB, 1, 64), (native.OPT_PIPE_SEARCH_RAYS, 0, 1 << 24),
+    (native.OPT_VIEW_SKIP, 0, 1), (native.OPT_VIEW_COMPACT, 0, 1))
+
+
 def test_set_option_validation():
+    """Every option refuses the value just below and just above its range and accepts both ends of it; SUPER_TILE
+    refuses 0, 3 and 8 and accepts 1, 2 and 4; numbers that name no option are refused."""
     sc = make_scene(n=16, W=32, H=24)
+    assert len({opt for opt, _, _ in _OPTION_RANGES}) == 14
     with _ctx_for(sc, S=4) as ctx:
-        for opt, bad in ((native.OPT_SEARCH_DEPTH, 7), (native.OPT_SEARCH_DEPTH, -1), (native.OPT_ROUND_BATCH, 0),
-                         (native.OPT_ROUND_BATCH, 65), (native.OPT_LONG_SAMPLES, -1), (native.OPT_SEARCH_OVERSUB, 0), (native.OPT_EXACT_SEARCH, 2), (native.OPT_TILE_ORDER, 2),
-                         (6, 0), (7, 0), (native.OPT_SUPER_TILE, 3), (native.OPT_REGROUP, 2), (native.OPT_EXACT_TILE_KEYS, 2),
-                         (native.OPT_PIPE_TRIGGER, 3), (native.OPT_PIPE_OVERSUB, 0), (native.OPT_PIPE_OVERSUB, 65),
-                         (native.OPT_PIPE_SEARCH_RAYS, -1), (native.OPT_PIPE_SEARCH_RAYS, (1 << 24) + 1),
-                         (99, 1)):   # 6, 7: ABI 6's fused modes
-            with pytest.raises(RuntimeError):
-                ctx.set_option(opt, bad)
-        ctx.set_option(native.OPT_SEARCH_DEPTH, 6)
-        ctx.set_option(native.OPT_PIPE_OVERSUB, 64)
+        for opt, lo, hi in _OPTION_RANGES:
+            for bad in (lo - 1, hi + 1):
+                with pytest.raises(RuntimeError, match=f"value {bad} out of range for option {opt}$"):
+                    ctx.set_option(opt, bad)
+            ctx.set_option(opt, lo)
+            ctx.set_option(opt, hi)
+        for bad in (0, 3, 8):
+            with pytest.raises(RuntimeError, match=f"value {bad} out of range for option {native.OPT_SUPER_TILE}$"):
+                ctx.set_option(native.OPT_SUPER_TILE, bad)
+        for good in (1, 2, 4):
+            ctx.set_option(native.OPT_SUPER_TILE, good)
+        for opt in (6, 7, 99, -1):   # 6, 7: ABI 6's fused modes
+            with pytest.raises(RuntimeError, match=f"unknown option {opt}$"):
+                ctx.set_option(opt, 1)
 
 
 def test_lut_sizes_checked_against_lds():

@@ -40,7 +40,7 @@ Which lines of vdi_generate.hip each group is aimed at:
   test_long_samples_sweep, test_queue_*     the two append indices of sample_tile (:1226-1233: the long rays'
       queue_count from the front, the short rays' queue_cap - 1 - (queue_short + ...) from the back), the search's
       qlong / qlen (:1352-1353) and its pop mapping r < qlong ? r : queue_cap - 1 - (r - qlong) (:1488), with
-      queue_cap = BV * W * H for one brick, three bricks and merged volumes (insitu_hip.cpp:762)
+      queue_cap = BV * W * H for one brick, three bricks and merged volumes (vdi_gen_params, insitu_hip.cpp)
   test_queue_shorter_than_a_wave            the pop's base + cnt >= qlen (:1477) and r < qlen (:1488) inside one claim
   test_round_batch*                         the round-end ballot (:1671-1677) with ROUND_BATCH 1 (a lane never waits),
       28 and 64 (a finished lane waits with k >= n while any lane of its wave replays: the `on = k < n` selects of
@@ -48,7 +48,8 @@ Which lines of vdi_generate.hip each group is aimed at:
       `hold` lanes (:1552) in the same ballot, and emit's nseg >= S branch (:1603) with the early k = n exit (:1637)
   test_two_renders_*, test_pipelined_*, test_small_cache_*    the counters zeroed per render, the pipelined search's
       block count (:1358-1364) and drain flag (:1477-1483), and waves that queue nothing (:1199-1219)
-  test_env_*                                the INSITU_* seeds of insitu_create (insitu_hip.cpp:440-457)
+  test_env_*                                the INSITU_* seeds of insitu_create (seed_options over the option table,
+      insitu_context.cpp)
 """
 from __future__ import annotations
 
@@ -465,12 +466,23 @@ def test_small_cache_waves_queue_nothing():
 
 
 # ---------------------------------------------------------------- 5. environment seeds
-@pytest.mark.parametrize("var,value", [("INSITU_LONG_SAMPLES", "-1"), ("INSITU_ROUND_BATCH", "65")])
+# every INSITU_* seed of insitu_create with a value outside its option's range (include/insitu_hip.h)
+_ENV_OUT_OF_RANGE = [
+    ("INSITU_EXACT_SEARCH", "2"), ("INSITU_SEARCH_DEPTH", "7"), ("INSITU_LONG_SAMPLES", "-1"),
+    ("INSITU_ROUND_BATCH", "65"), ("INSITU_SEARCH_OVERSUB", "0"), ("INSITU_TILE_ORDER", "2"),
+    ("INSITU_SUPER_TILE", "3"), ("INSITU_REGROUP", "-1"), ("INSITU_EXACT_TILE_KEYS", "2"),
+    ("INSITU_PIPE_TRIGGER", "3"), ("INSITU_PIPE_OVERSUB", "65"), ("INSITU_PIPE_SEARCH_RAYS", "16777217"),
+    ("INSITU_VIEW_SKIP", "2"), ("INSITU_VIEW_COMPACT", "-1")]
+
+
+@pytest.mark.parametrize("var,value", _ENV_OUT_OF_RANGE)
 def test_env_seed_out_of_range(monkeypatch, var, value):
-    """insitu_create refuses an out-of-range INSITU_* seed and names the variable."""
+    """insitu_create refuses an out-of-range INSITU_* seed, whichever of the 14 it is, and names the variable and
+    the value."""
     monkeypatch.setenv(var, value)
-    with pytest.raises(RuntimeError, match=f"{var}={value} out of range"):
-        _context("deep")
+    sc = make_scene(n=16, W=32, H=24)
+    with pytest.raises(RuntimeError, match=f"insitu_create: {var}={value} out of range$"):
+        InSituContext(sc["W"], sc["H"], max_supersegments=4)
 
 
 def test_env_seeds_and_override(monkeypatch):
