@@ -143,6 +143,62 @@ __host__ __device__ __forceinline__ float det_exp2(float y) {
 __host__ __device__ __forceinline__ float det_pow(float x, float y) { return det_exp2(y * det_log2(x)); }
 __host__ __device__ __forceinline__ float det_ln(float x) { return det_log2(x) * 0.693147182f; }
 
+// ---- det_pow without its special-value selects ----
+// For a finite positive normal x, det_log2's selects are identities (no subnormal scaling, x is not inf, 0 or
+// negative); for an exponent t = y * log2(x) in [kPowNormalLo, kPowNormalHi], det_exp2's are: rint(t) lies in
+// [-125, 127], so the +-200 clamp keeps it, ea = ni and b = 1.0f ((p * 2^ni) * 1.0f has the bits of p * 2^ni),
+// and none of t < -150, t >= 128, NaN holds.  What is left are det_pow's own operations on the same values:
+// det_pow_normal(x, y) == det_pow(x, y) bit for bit wherever det_pow_normal_ok(x, y) holds
+// (tests/test_pow_fast_host.py).  The range stays a whole unit inside [-126, 127.5), the exponents whose 2^ni
+// is one normal factor.
+constexpr float kPowNormalLo = -125.0f, kPowNormalHi = 127.0f;
+__host__ __device__ __forceinline__ float det_log2_normal(float x) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, x);
+    int e = (int)((u >> 23) & 0xffu) - 127;
+    float m = __builtin_bit_cast(float, (u & 0x007fffffu) | 0x3f800000u);
+    const bool big = m > 1.41421354f;
+    m = big ? m * 0.5f : m;
+    e += big ? 1 : 0;
+    const float f = m - 1.0f;
+#ifdef __HIP_DEVICE_COMPILE__
+    const float dd = 2.0f + f;   // f / (2 + f) as in det_log2
+    float y = __builtin_amdgcn_rcpf(dd);
+    y = __builtin_fmaf(__builtin_fmaf(-dd, y, 1.0f), y, y);
+    float s = f * y;
+    s = __builtin_fmaf(__builtin_fmaf(-dd, s, f), y, s);
+    s = __builtin_fmaf(__builtin_fmaf(-dd, s, f), y, s);
+#else
+    const float s = f / (2.0f + f);
+#endif
+    const float z = s * s;
+    float p = __builtin_fmaf(z, 0.0909090936f, 0.111111112f);
+    p = __builtin_fmaf(z, p, 0.142857149f);
+    p = __builtin_fmaf(z, p, 0.200000003f);
+    p = __builtin_fmaf(z, p, 0.333333343f);
+    const float s2 = s + s;
+    const float ln = __builtin_fmaf(s2 * z, p, s2);
+    return __builtin_fmaf(ln, 1.44269502f, (float)e);
+}
+// the guard: x a finite positive normal and y * log2(x) in the closed range (a NaN product fails both compares)
+__host__ __device__ __forceinline__ bool det_pow_normal_ok(float x, float y) {
+    const float t = y * det_log2_normal(x);
+    return x >= 1.17549435e-38f && x < __builtin_inff() && t >= kPowNormalLo && t <= kPowNormalHi;
+}
+__host__ __device__ __forceinline__ float det_pow_normal(float x, float y) {
+    const float t = y * det_log2_normal(x);
+    const float n = __builtin_rintf(t);
+    const float f = t - n;
+    float p = 1.52527336e-05f;
+    p = __builtin_fmaf(p, f, 1.54035297e-04f);
+    p = __builtin_fmaf(p, f, 1.33335581e-03f);
+    p = __builtin_fmaf(p, f, 9.61812911e-03f);
+    p = __builtin_fmaf(p, f, 5.55041087e-02f);
+    p = __builtin_fmaf(p, f, 2.40226507e-01f);
+    p = __builtin_fmaf(p, f, 6.93147182e-01f);
+    p = __builtin_fmaf(p, f, 1.0f);
+    return p * __builtin_bit_cast(float, (uint32_t)((int)n + 127) << 23);
+}
+
 // Smallest float y with sqrt_rn(y) >= t (t >= 0): since correctly rounded sqrt is monotone,
 // `sqrt(y) >= t` is exactly `y >= sq_threshold(t)`, which turns the supersegment test
 // length(...) >= threshold (AccumulateVDI.comp:74, VDICompositor.comp:350) into a compare of
@@ -177,6 +233,14 @@ __device__ __forceinline__ float sumsq3(float x, float y, float z) {
 
 // VDIGenerator.comp:80-82
 __device__ __forceinline__ float adjust_opacity(float a, float len) { return 1.0f - det_pow(1.0f - a, len); }
+// The same for the lanes of a wave that are active at the call: det_pow_normal when its guard holds for every one
+// of them (one wave-uniform branch; every sample of an ordinary transfer function), det_pow for all otherwise
+// (an opaque sample: 1 - a = 0; an out-of-range opacity).  The same bits either way.
+__device__ __forceinline__ float adjust_opacity_wave(float a, float len) {
+    const float om = 1.0f - a;
+    if (__ballot(!det_pow_normal_ok(om, len)) == 0ull) return 1.0f - det_pow_normal(om, len);
+    return 1.0f - det_pow(om, len);
+}
 
 __device__ __forceinline__ uint32_t unorm8(float x) {
     float q = (x > 0.0f) ? ((x < 1.0f) ? x : 1.0f) : 0.0f;

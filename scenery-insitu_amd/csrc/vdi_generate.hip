@@ -351,13 +351,12 @@ __device__ __forceinline__ void seg_sample_sel(SegState& s, const f4 xv, const f
 // VGPRs per threshold (the kernel then fits 4 waves per SIMD); lo_a, hi_a as in SegState.
 struct CountStateL {
     f4 curV;
-    int steps_in, nterm;
-    bool open;
+    int steps_in, nterm;   // steps_in > 0: a supersegment is open (an open one has accumulated a sample)
     float lo_a, hi_a;
+    __device__ __forceinline__ bool open() const { return steps_in > 0; }
     __device__ __forceinline__ void reset() {
         curV = f4{0.0f, 0.0f, 0.0f, 0.0f};
         steps_in = nterm = 0;
-        open = false;
         lo_a = -1.0f;
         hi_a = __builtin_inff();
     }
@@ -368,32 +367,113 @@ __device__ __forceinline__ void count_sample_l(CountStateL& s, float* bnd, const
                                                const Thr& th, const f4& wfront, const f4& wback, const float nw) {
     if (!(xv.x > -0.5f || last)) return;
     const bool transparent = wv <= 0.0f;
-    if (s.open) {
+    if (s.open()) {
         float b;
         bool est = false;
         if (close_decision<FILTERED>(s.curV, s.steps_in, xv, wfront, wback, nw, th, b, est)) {
             if (est) s.hi_a = __builtin_fminf(s.hi_a, b);
             else bnd[256] = __builtin_fminf(bnd[256], b);
             s.nterm++;
-            s.open = false;
             s.steps_in = 0;
         } else {
             if (est) s.lo_a = __builtin_fmaxf(s.lo_a, b);
             else bnd[0] = __builtin_fmaxf(bnd[0], b);
         }
     }
-    if (!s.open && !transparent) {
-        s.open = true;
-        s.curV = f4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
-    if (s.open) {
+    const bool opening = !s.open() && !transparent;
+    if (opening) s.curV = f4{0.0f, 0.0f, 0.0f, 0.0f};
+    if (s.open() || opening) {
         s.curV = accumulate(s.curV, xv, wv);
         s.steps_in++;
+        if (last) {   // (closed: nothing reads the state of a ray's last supersegment)
+            s.nterm++;
+            s.steps_in = 0;
+        }
     }
-    if (last && s.open) {
+}
+
+// Two levels as one machine.  Until one of two thresholds closes a supersegment where the other does not, the
+// two count_sample_l machines are in the same state -- curV, steps_in and nterm agree bit for bit, and so
+// do their estimates and exact values.  Spine levels 1 and 2 (0.866 and 0.433) almost never close, so
+// first_pass_impl keeps them as ONE state (s1: level 2's registers) while they agree and runs one estimate, at
+// most one exact value and one state update per sample for both.  What each level keeps for itself is the
+// bookkeeping of its own decisions: the extreme estimates (lo_a / hi_a) where its own thresholds let the
+// estimate decide, its own LDS bounds (bnd0, bnd1) where they did not.
+// count_apply_l: what count_sample_l does with its decision (o: the supersegment was open and the sample
+// counts, c: it closes, est / b as close_decision's)
+__device__ __forceinline__ void count_apply_l(CountStateL& s, float& lo_a, float& hi_a, float* bnd, const bool v,
+                                              const bool o, const bool c, const bool est, const float b, const f4 xv,
+                                              const float wv, const bool last, const bool update) {
+    if (o) {
+        if (c) {
+            if (est) hi_a = __builtin_fminf(hi_a, b);
+            else bnd[256] = __builtin_fminf(bnd[256], b);
+        } else {
+            if (est) lo_a = __builtin_fmaxf(lo_a, b);
+            else bnd[0] = __builtin_fmaxf(bnd[0], b);
+        }
+    }
+    if (!update) return;   // (the pair: the other level's call updates the one state)
+    if (o && c) {
         s.nterm++;
-        s.open = false;
+        s.steps_in = 0;
     }
+    if (v) {
+        const bool opening = !s.open() && !(wv <= 0.0f);
+        if (opening) s.curV = f4{0.0f, 0.0f, 0.0f, 0.0f};
+        if (s.open() || opening) {
+            s.curV = accumulate(s.curV, xv, wv);
+            s.steps_in++;
+            if (last) {
+                s.nterm++;
+                s.steps_in = 0;
+            }
+        }
+    }
+}
+// One sample for the paired levels (s0: level 1, of which only lo_a / hi_a are in use; s1: the state).  When some
+// lane of the wave at this sample decides differently for the two levels (the ballot is over the active lanes),
+// the pair splits for all of them: s0 takes a copy of the state and each level applies its own decision.
+// Returns whether the levels are still paired.  both == false (wave-uniform: some lane's levels have split, and
+// level 1 ran its own count_sample_l): s1's machine alone, count_sample_l's operations -- the one copy of level 2's
+// machine in the code serves both modes (a second copy cost the sampling kernel 12 VGPRs).
+template <bool FILTERED>
+__device__ __forceinline__ bool count_sample_pair(CountStateL& s0, CountStateL& s1, float* bnd0, float* bnd1, const int S,
+                                                  const f4 xv, const float wv, const bool last, const Thr& th0,
+                                                  const Thr& th1, const f4& wfront, const f4& wback, const float nw,
+                                                  const bool both) {
+    const bool v = s1.nterm <= S && (xv.x > -0.5f || last);
+    const bool o = v && s1.open();
+    bool c0 = false, c1 = false, e0 = false, e1 = false;
+    float a = 0.0f, ex = 0.0f;
+    if (o) {
+        if constexpr (FILTERED) {   // close_decision's filter, against both levels' thresholds
+            a = approx_diff_sq(s1.curV, s1.steps_in, xv, wfront, wback, nw);
+            c1 = a >= th1.hi && a < 1.0e30f;
+            e1 = c1 || a < th1.lo;
+            if (both) {
+                c0 = a >= th0.hi && a < 1.0e30f;
+                e0 = c0 || a < th0.lo;
+            }
+        }
+        if (!e1 || (both && !e0)) {
+            ex = exact_diff_sq(exact_adjusted(s1.curV, s1.steps_in, wfront, wback, nw), xv);
+            if (!e1) c1 = ex >= th1.sq;
+            if (both && !e0) c0 = ex >= th0.sq;
+        }
+    }
+    bool split = false;
+    if (both) {
+        split = __ballot(c0 != c1) != 0ull;
+        if (split) {
+            s0.curV = s1.curV;
+            s0.steps_in = s1.steps_in;
+            s0.nterm = s1.nterm;
+        }
+        count_apply_l(s0, s0.lo_a, s0.hi_a, bnd0, v, o, c0, e0, e0 ? a : ex, xv, wv, last, split);
+    }
+    count_apply_l(s1, s1.lo_a, s1.hi_a, bnd1, v, o, c1, e1, e1 ? a : ex, xv, wv, last, true);
+    return both && !split;
 }
 
 // Thresholds of the search tree below a node: child 2i+1 follows "n > S" (low = mid), child
@@ -539,7 +619,7 @@ __device__ __forceinline__ void march_pass(const VdiGenParams& P, const BrickDes
             const f4 x = classify_sample(sc_cur, s_tf, P.xfer.n_tf, s_cm, P.xfer.n_cm);
             float w = 0.0f;
             if (x.x > -0.5f || last)
-                w = adjust_opacity(x.w, len4(wpos.x - wprev.x, wpos.y - wprev.y, wpos.z - wprev.z, wpos.w - wprev.w));
+                w = adjust_opacity_wave(x.w, len4(wpos.x - wprev.x, wpos.y - wprev.y, wpos.z - wprev.z, wpos.w - wprev.w));
             if (!sample_fn(i, sc_cur, x, w, step, last)) break;
         }
         sc_cur = voxel_coord(brick, nxt);
@@ -689,7 +769,7 @@ __device__ void merge_search_in_place(const VdiGenParams& P, const float* s_tf, 
                     const f4 x = classify_sample(sc, s_tf, P.xfer.n_tf, s_cm, P.xfer.n_cm);
                     float w = 0.0f;
                     if (x.x > -0.5f || last)
-                        w = adjust_opacity(x.w, len4(wpos.x - wprev.x, wpos.y - wprev.y, wpos.z - wprev.z, wpos.w - wprev.w));
+                        w = adjust_opacity_wave(x.w, len4(wpos.x - wprev.x, wpos.y - wprev.y, wpos.z - wprev.z, wpos.w - wprev.w));
                     seg_sample(st, x, w, step, ndc_of, last, th, R.wfront, R.wback, nw, emit);
                     // a search pass that has closed more than S supersegments is decided (:511-514)
                     if (!write && st.nterm > S) {
@@ -753,7 +833,7 @@ __device__ __forceinline__ void march_multi(const VdiGenParams& P, const float* 
             const f4 x = classify_sample(sc, s_tf, P.xfer.n_tf, s_cm, P.xfer.n_cm);
             float w = 0.0f;
             if (x.x > -0.5f || last)
-                w = adjust_opacity(x.w, len4(wpos.x - wprev.x, wpos.y - wprev.y, wpos.z - wprev.z, wpos.w - wprev.w));
+                w = adjust_opacity_wave(x.w, len4(wpos.x - wprev.x, wpos.y - wprev.y, wpos.z - wprev.z, wpos.w - wprev.w));
             const bool go = sample_fn(i, sc, x, w, step, last);
             flush_fn();
             if (!go) return;
@@ -848,6 +928,8 @@ __device__ bool first_pass_impl(const VdiGenParams& P, const f4& wfront, const f
     float step_first = 0.0f;
     bool last_final = false;
     bool store_chunk = false;   // the chunk (in LDS, chk) is stored whole (2 x 16 B) once complete
+    // levels 1 and 2 still agree: their one state is cs[1]'s, and of cs[0] only lo_a / hi_a are in use
+    bool paired = K >= 2;
     march([&](int i, float sc, const f4& x, float w, float stp, bool last) {
         // cache chunk layout: 4 samples per 32 B = {coord x4, opacity x4}
         const int j = k & 3;
@@ -880,8 +962,24 @@ __device__ bool first_pass_impl(const VdiGenParams& P, const f4& wfront, const f
         // samples seen so far, which is all the "n > S" conclusion rests on (every threshold in it
         // closes the same S + 1 supersegments over that prefix).
         if (st.nterm <= S) count_sample_l<FILTERED>(st, bl, x, w, last, th1, wfront, wback, nw);
+        if constexpr (K >= 2) {
+            // levels 1 and 2 as one machine (count_sample_pair) while every lane of the wave at this sample has
+            // them paired; the first sample they decide differently on splits the pair for those lanes
+            const bool both = __ballot(!paired) == 0ull;
+            if (!both) {
+                if (paired) {   // a lane that was not at the sample the others split on
+                    cs[0].curV = cs[1].curV;
+                    cs[0].steps_in = cs[1].steps_in;
+                    cs[0].nterm = cs[1].nterm;
+                    paired = false;
+                }
+                if (cs[0].nterm <= S) count_sample_l<FILTERED>(cs[0], bl + 512, x, w, last, tk[0], wfront, wback, nw);
+            }
+            paired = count_sample_pair<FILTERED>(cs[0], cs[1], bl + 512, bl + 1024, S, x, w, last, tk[0], tk[1], wfront,
+                                                 wback, nw, both);
+        }
 #pragma unroll
-        for (int l = 0; l < K; ++l)
+        for (int l = K >= 2 ? 2 : 0; l < K; ++l)
             if (cs[l].nterm <= S)
                 count_sample_l<FILTERED>(cs[l], bl + 512 * (l + 1), x, w, last, tk[l], wfront, wback, nw);
         return true;   // the cache needs every sample
@@ -900,6 +998,7 @@ __device__ bool first_pass_impl(const VdiGenParams& P, const f4& wfront, const f
     if constexpr (MERGED) {
         if (overflow) return false;
     }
+    if (paired) cs[0].nterm = cs[1].nterm;   // never split: level 1 closed what level 2 closed
     if ((k & (PAIRS ? 7 : 3)) != 0 && !last_final) {   // flush a partial chunk (the ray left the brick early)
         const float4 bc = *reinterpret_cast<const float4*>(chk), bw = *reinterpret_cast<const float4*>(chk + 4);
         if constexpr (PAIRS) {
@@ -1235,7 +1334,10 @@ __device__ __forceinline__ void sample_tile(const VdiGenParams& P, const float* 
     }
 }
 
-constexpr int kSampleMinBlocks = 3;   // 3 waves per SIMD (<= 168 VGPRs): measured 10.3 vs 11.4 ms at 2 waves
+// 4 waves per SIMD (<= 128 VGPRs).  The kernel allocates 125 VGPRs, none spilled, under a bound of 3 as well: the
+// bound states the requirement, the fit is the code's own.  Waves per SIMD measured: 2 -> 3 11.4 ->
+// 10.3 ms (round 2), 3 -> 4 sampling 7.95 -> 7.54 ms (round 5)
+constexpr int kSampleMinBlocks = 4;
 template <int DT, bool FILTERED>
 __global__ __launch_bounds__(256, kSampleMinBlocks) void vdi_sample_kernel(const VdiGenParams P) {
     extern __shared__ __attribute__((aligned(16))) float4 smem[];
